@@ -22,7 +22,10 @@ The cycle is then fp64-issue-bound: the roofline is the fp64 operations the laun
 executes (pamg_vcycle_flops x cycles) over its duration against the 78.6 TFLOP/s
 fp64 peak. The other schedules (one HBM-bound launch per cycle: the round-1 form, with
 its HBM roofline), the reference's own operation order (arith = 0, bitwise equal
-to the reference) and the other workloads are timed and reported under "extra".
+to the reference) and the other workloads are timed and reported under "extra"
+with --full only, like the CPU baseline, the HBM sweep rooflines and the time
+loop. A plain run sets up, warms up, times --steps cycles (one pamg_vcycle call)
+and prints the line; --dump-outputs DIR writes the state that call left.
 
 N > 1 (python -m torch.distributed.run ... bench.py --gpus N): strong scaling
 of the same mesh, x-strip domain decomposition by unstructured element, one
@@ -61,6 +64,12 @@ EVENT_STRIDE = 10
 RENDEZVOUS_S = int(os.environ.get("PAMG_BENCH_RENDEZVOUS_S", "300"))
 ALL_CLASSES = 0x2FF7F   # every timing class (PAMG_K_*) but sweep_bench (bit 16 face_fallback counts regardless)
 SWEEP_LAUNCHES = 60    # launches of each level-1 HBM sweep roofline measurement
+SIDE_STEPS_MAX = 2000  # cycles (timed, and of warm-up) of each side measurement of a --full run, at most
+SETTLE_S = 0.2         # V-cycles on a second handle ahead of the warm-up of a run without side measurements
+SETTLE_CYCLES = 200    # cycles of each of its calls
+DUMP_SAMPLE = 1 << 20  # --dump-outputs: values written of a larger array (a fixed sample, seed DUMP_SEED)
+DUMP_BYTES = 48 << 20  # and of all arrays together
+DUMP_SEED = 20251019
 
 
 def parse():
@@ -75,8 +84,18 @@ def parse():
     ap.add_argument("--levels", type=int, default=3)
     ap.add_argument("--nsmooth", type=int, default=4)
     ap.add_argument("--mesh", default=MESH)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the n_split=3 and sweep-kernel side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline, the level-1 sweep rooflines, "
+                         "the time loop, the other schedules, arithmetic, sizes and operators (cpu_baseline, "
+                         "roofline_hbm_smoother, time_loop and most of extra in the result line); a plain run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state the timed call left (tnew and the residual of every level) "
+                         "as DIR/<name>.npy, float64; arrays above DUMP_SAMPLE values as a fixed seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the n_split=3 and sweep-kernel side measurements; without: skip the "
+                         "V-cycles a plain run issues on a second handle ahead of the warm-up to settle the clocks")
     ap.add_argument("--extras-after", action="store_true",
                     help="run the side measurements after the timed region instead of before the warm-up")
     ap.add_argument("--halo-mode", type=int, default=0)
@@ -93,7 +112,13 @@ def parse():
                     help="3: pipelined fused launches, level 1 of cycle c + coarse levels of cycle c+1 in one "
                          "launch (default); 1: two fused launches per V-cycle; 2: the same, concurrent on two "
                          "streams; 0: per-step kernels")
-    return ap.parse_args()
+    a = ap.parse_args()
+    # a plain run settles the clocks ahead of the warm-up (main); an explicit --no-extra keeps the run to the
+    # warm-up and the timed call alone, as the profiling scripts expect
+    a.settle = not a.full and not a.no_extra
+    if not a.full:
+        a.no_extra = a.no_cpu_baseline = True
+    return a
 
 
 def host_cpu():
@@ -425,6 +450,23 @@ def measure_corrected(pamg, m, S, L, ns, arith, device, cycles=200):
     return out
 
 
+def dump_outputs(s, d, rank, world):
+    """--dump-outputs: what a caller of the timed pamg_vcycle(steps) call reads back, tnew and the residual of
+    every level (this rank's partition; <name>_rank<r>.npy with several ranks), float64. An array of more than
+    DUMP_SAMPLE values is written as its values at DUMP_SAMPLE positions drawn once from a fixed seed (the
+    same positions in every run of the same configuration), so a dump stays under 64 MB."""
+    import pamg.solver as P
+    os.makedirs(d, exist_ok=True)
+    fields = [(f"{name}_L{l}", what, l) for l in range(1, s.levels + 1)
+              for name, what in (("tnew", P.TNEW), ("res", P.RESIDUAL))]
+    cap = min(DUMP_SAMPLE, DUMP_BYTES // (8 * len(fields)))
+    for name, what, l in fields:
+        v = s.get(what, l).reshape(-1, order="F")
+        if v.size > cap:
+            v = v[np.random.default_rng(DUMP_SEED).integers(0, v.size, cap)]
+        np.save(os.path.join(d, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), np.ascontiguousarray(v))
+
+
 def comm_report(s, world, dist):
     kind, ver, path = s.comm_info()
     mine = {"transport": kind, "rccl_version": ver, "librccl": path}
@@ -437,6 +479,9 @@ def comm_report(s, world, dist):
 
 def main():
     a = parse()
+    # the side measurements (--full) time --steps cycles after --warmup as the headline does, up to SIDE_STEPS_MAX:
+    # the per-step kernel sequence runs ~0.8 ms per cycle, and a --full run has to stay a matter of minutes
+    side_steps, side_warmup = min(a.steps, SIDE_STEPS_MAX), min(a.warmup, SIDE_STEPS_MAX)
     time_loop = None
     roofline_hbm = None
     extra_pre = {}
@@ -508,16 +553,16 @@ def main():
                                         fused=a.fused, arith=a.arith)
         s1.set_call_schedule(1)
         s1.begin_timestep()
-        s1.vcycle(a.warmup)
+        s1.vcycle(side_warmup)
         s1.synchronize()
         t0 = time.perf_counter()
-        s1.vcycle(a.steps)
+        s1.vcycle(side_steps)
         s1.synchronize()
-        v1 = a.steps / (time.perf_counter() - t0)
+        v1 = side_steps / (time.perf_counter() - t0)
         s1.timing_enable(ALL_CLASSES)
         s1.timing_stride(EVENT_STRIDE)
         s1.timing_reset()
-        s1.vcycle(a.steps)
+        s1.vcycle(side_steps)
         s1.synchronize()
         kp = s1.timing()["vcycle_pipe"]
         if kp["launches"]:
@@ -555,22 +600,22 @@ def main():
             su = pamg.SemiImplicitIterative(mesh, a.nsplit, a.levels, n_smooth=a.nsmooth, solver=3, device=device,
                                             **kw)
             su.begin_timestep()
-            su.vcycle(a.warmup)
+            su.vcycle(side_warmup)
             su.synchronize()
             t0 = time.perf_counter()
-            su.vcycle(a.steps)
+            su.vcycle(side_steps)
             su.synchronize()
-            ex[f"{tag}_vcycles_per_s"] = round(a.steps / (time.perf_counter() - t0), 2)
+            ex[f"{tag}_vcycles_per_s"] = round(side_steps / (time.perf_counter() - t0), 2)
             su.close()
         s3 = pamg.SemiImplicitIterative(mesh, 3, a.levels, n_smooth=a.nsmooth, solver=3, device=device,
                                         arith=a.arith)
         s3.begin_timestep()
-        s3.vcycle(a.warmup)
+        s3.vcycle(side_warmup)
         s3.synchronize()
         t0 = time.perf_counter()
-        s3.vcycle(max(a.steps, 200))
+        s3.vcycle(max(side_steps, 200))
         s3.synchronize()
-        ex["nsplit3_vcycles_per_s"] = round(max(a.steps, 200) / (time.perf_counter() - t0), 1)
+        ex["nsplit3_vcycles_per_s"] = round(max(side_steps, 200) / (time.perf_counter() - t0), 1)
         # config 3 driven as the reference drives it: pamg_run(50, 2), one resident launch
         s3.run(5, 2)
         s3.synchronize()
@@ -594,6 +639,19 @@ def main():
         time_loop = measure_time_loop(s)
         return ex
 
+    settle = None
+    if world == 1 and a.settle:
+        # a plain run has no side measurements ahead of the warm-up: a second handle of the same workload runs V-cycles for
+        # SETTLE_S first (the timed handle's state stays begin_timestep + warm-up + steps), so that the timed call
+        # starts on settled clocks as it does after the side measurements
+        # (profiles/r05_q_prework_probe.txt: 0.0522 ms per cycle from idle, 0.0463 after 150 ms of this work)
+        settle = pamg.SemiImplicitIterative(mesh, a.nsplit, a.levels, n_smooth=a.nsmooth, solver=3, device=device,
+                                            fused=a.fused, arith=a.arith)
+        settle.begin_timestep()
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < SETTLE_S:
+            settle.vcycle(SETTLE_CYCLES)
+            settle.synchronize()
     extra_other = {}
     if rank == 0 and world == 1 and not a.no_extra and not a.extras_after:
         # before the warm-up (default): the timed call then starts on a GPU that has been running this
@@ -645,6 +703,11 @@ def main():
         rank_elapsed = [None] * world
         dist.all_gather_object(rank_elapsed, t1 - t0)
         barrier()
+    if settle is not None:
+        settle.close()
+    if a.dump_outputs:
+        # before anything else runs on the handle: the state as the timed call left it
+        dump_outputs(s, a.dump_outputs, rank, world)
     if not live_events:
         # per-launch events time each launch on its own: the post-pass runs the pipelined
         # calls as one launch per cycle (the timed region ran the partition's automatic
@@ -709,16 +772,16 @@ def main():
                                         halo_mode=a.halo_mode, comm=comm_for(mode), fused=a.fused, arith=a.arith,
                                         halo_exchange=mode)
         sx.begin_timestep()
-        sx.vcycle(a.warmup)
+        sx.vcycle(side_warmup)
         sx.synchronize()
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        sx.vcycle(a.steps)
+        sx.vcycle(side_steps)
         sx.synchronize()
         t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        extra[f"halo_exchange{mode}_vcycles_per_s"] = round(a.steps / float(t.item()), 2)
+        extra[f"halo_exchange{mode}_vcycles_per_s"] = round(side_steps / float(t.item()), 2)
         extra[f"halo_exchange{a.halo_exchange}_vcycles_per_s"] = round(value, 2)
         sx.close()
     cpu = None

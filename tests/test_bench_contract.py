@@ -9,15 +9,49 @@ import pytest
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 
 
+def check_dumped_outputs(out, steps, warmup, nsplit):
+    """--dump-outputs wrote the state a begin_timestep, a warm-up call and the timed call leave on bench.py's
+    default workload (bitwise: the same library, the same calls), a larger array at bench.py's seeded sample"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    import pamg
+    import pamg.solver as P
+    s = pamg.SemiImplicitIterative(pamg.Mesh.read(bench.MESH), nsplit, 3, n_smooth=4, solver=3, arith=1, fused=3)
+    s.begin_timestep()
+    s.vcycle(warmup)
+    s.vcycle(steps)
+    s.synchronize()
+    names = sorted(f"{n}_L{l}.npy" for l in (1, 2, 3) for n in ("tnew", "res"))
+    assert sorted(os.listdir(out)) == names
+    total = 0
+    for l in (1, 2, 3):
+        for n, what in (("tnew", P.TNEW), ("res", P.RESIDUAL)):
+            got = np.load(os.path.join(out, f"{n}_L{l}.npy"))
+            want = s.get(what, l).reshape(-1, order="F")
+            if want.size > bench.DUMP_SAMPLE:
+                want = want[np.random.default_rng(bench.DUMP_SEED).integers(0, want.size, bench.DUMP_SAMPLE)]
+            assert got.dtype == np.float64 and got.shape == want.shape
+            assert np.array_equal(got, want), (n, l)
+            total += got.nbytes
+    assert np.abs(np.load(os.path.join(out, "tnew_L1.npy"))).max() > 0
+    assert total <= 64 << 20
+    s.close()
+
+
 @pytest.mark.gpu
-def test_bench_prints_the_contract_line():
+def test_bench_prints_the_contract_line(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
-                        "--nsplit", "3", "--no-extra", "--no-cpu-baseline"],
+                        "--nsplit", "3", "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out")],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
+    # a plain run (no --full) measures nothing beside its headline figure
+    assert d["cpu_baseline"] is None and d["time_loop"] is None and d["roofline_hbm_smoother"] is None
+    assert "sweep_assembled" not in d["extra"] and "op1" not in d["extra"]
+    check_dumped_outputs(tmp_path / "out", steps=4, warmup=2, nsplit=3)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
               "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
