@@ -80,8 +80,12 @@ typedef struct pamg_mesh pamg_mesh;
 typedef struct {
     int n_split;      /* transport_tri_semi.F90:118 */
     int multi_levels; /* main.F90:46-47 (multi_levels <= n_split, :120-123) */
-    int n_smooth;     /* sweeps per smoother call, main.F90:46-47 */
-    int n_coarse;     /* smoother calls on the coarsest level, :351 (15) */
+    int n_smooth;     /* sweeps per smoother call, main.F90:46-47; >= 1 (any count above 4 included). 0 is
+                         PAMG_ERR_ARG: the reference's sweep loop (:548-721) is then empty, and since get_RHS is
+                         called only inside it (:699-701, :710-712) level 1's right-hand side is never assembled
+                         and no update (:491-507) ever runs -- a cycle that solves nothing, so it is refused */
+    int n_coarse;     /* smoother calls on the coarsest level, :351 (15); >= 0 (0: the coarsest level is only
+                         restricted to, never swept) */
     int solver;       /* 1 Jacobi, 2 Richardson, 3 Gauss-Seidel (:695-716) */
     int device;       /* HIP device ordinal */
     double dt;        /* CFL*dx, :133 */
@@ -107,7 +111,9 @@ typedef struct {
                          1: contracted -- A_e = (1/dt) M + Kd assembled once per un_ele (fp64, host),
                             one fma chain per row: 12 fp64 operations per sub-element sweep instead
                             of 39; within 1e-13 relative of the reference (the north star's bar
-                            is 1e-10), bitwise equal between the fused and per-step schedules */
+                            is 1e-10; measured <= 9e-15 also where diffusion dominates the mass term,
+                            dt = 0.05, k = 3: DESIGN.md 2), bitwise equal between the fused and per-step
+                            schedules */
     int halo_exchange; /* multi-rank fused V-cycle: 0 (default) the RCCL exchange of the level-1 halo
                           words runs once per pamg_vcycle call, after its last cycle -- every cycle
                           rewrites every halo word and nothing in the cycle reads t_overlap, so only

@@ -21,7 +21,10 @@ Patches (each is an exact, asserted string replacement):
   run-time configuration (values hard-coded in the reference):
     mesh path :99, n_split :118, ntime :135 and the mode-9 arguments
     (main.F90:46-47: n_multigrid, vtk_interval, solver, multi_levels, n_smooth)
-    are read from `pamg_ref.nml` by oracle/ref_hooks/pamg_ref_hooks.F90
+    are read from `pamg_ref.nml` by oracle/ref_hooks/pamg_ref_hooks.F90; so are
+    the physics and cycle literals dt :133 (pamg_dt > 0 overrides CFL*dx),
+    k :136, omga :140 and the coarsest level's `do i=1,15` :351 (pamg_ncoarse),
+    whose namelist defaults are the reference's own values
   defined start state (the reference reads memory it never initialised):
     residuale / told / RHS / source of every level (:181-186; residuale is read
     by the first restriction, :336), t_overlap_old (:198) and
@@ -112,6 +115,10 @@ def patch_semi(t):
                "      call ReadMSH(meshList,trim(pamg_mesh),ierr, totnodes)\n", label="mesh")
     body = sub(body, "      n_split = 1\n", "      n_split = pamg_nsplit\n", label="n_split")
     body = sub(body, "      ntime = 2!time/dt\n", "      ntime = pamg_ntime\n", label="ntime")
+    body = sub(body, "      dt = CFL*dx\n", "      dt = CFL*dx\n      if (pamg_dt > 0.0) dt = pamg_dt\n", label="dt")
+    body = sub(body, "      k = 1. !diffusion", "      k = pamg_k !diffusion", label="k")
+    body = sub(body, "      omga = 0.8\n", "      omga = pamg_omega\n", label="omega")
+    body = sub(body, "          do i=1,15\n", "          do i=1,pamg_ncoarse\n", label="n_coarse")
     body = sub(body, "        allocate(tracer(i)%source(nloc,totele_str,totele_unst))\n",
                "        allocate(tracer(i)%source(nloc,totele_str,totele_unst))\n"
                "        tracer(i)%residuale = 0.0; tracer(i)%told = 0.0\n"

@@ -998,6 +998,8 @@ orc_state *orc_create(const orc_cfg *cfg, int U, const double *X, const int *reg
                       const int *fneig, const int *dir) {
     if (cfg->levels < 1 || cfg->levels > cfg->n_split || cfg->n_split > 12) return NULL;  /* :120-123 */
     if (cfg->theta != 1.0) return NULL;   /* theta hard-coded to 1 (:117); the theta<1 RHS is iterate-dependent */
+    /* n_smooth = 0 empties the sweep loop (:548-721): get_RHS (:699-701) never runs, nothing is solved */
+    if (cfg->n_smooth < 1 || cfg->n_coarse < 0 || !(cfg->dt > 0)) return NULL;
     orc_state *s = calloc(1, sizeof *s);
     s->c = *cfg;
     s->U = U;

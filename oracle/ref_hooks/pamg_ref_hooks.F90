@@ -4,7 +4,8 @@
 ! (oracle/build_ref.py). They give the reference's mode-9 driver
 ! (transport_tri_semi.F90:14-891) a run-time configuration instead of its
 ! hard-coded mesh path / n_split / ntime (transport_tri_semi.F90:99,118,135 and
-! main.F90:46-47) and write the driver's state as binary records so that the
+! main.F90:46-47) and of its dt / k / omga / coarse call count (:133,136,140,351)
+! and write the driver's state as binary records so that the
 ! build's HIP path can be compared at full fp64 precision (the reference's own
 ! VTU output is F12.10 text, get_vtk_files.F90:50-52, too coarse for parity).
 !
@@ -21,8 +22,13 @@ module pamg_ref_hooks
   integer :: pamg_solver = 3, pamg_levels = 1, pamg_nsmooth = 4
   integer :: pamg_vtk = 100000, pamg_dump_calls = 0
   integer :: pamg_call_counter = 0
+  ! the reference's literals (transport_tri_semi.F90:133,136,140,351) as defaults;
+  ! pamg_dt <= 0 keeps dt = CFL*dx
+  real :: pamg_dt = 0.0, pamg_k = 1., pamg_omega = 0.8
+  integer :: pamg_ncoarse = 15
   namelist /pamg_ref/ pamg_mesh, pamg_dump_prefix, pamg_nsplit, pamg_ntime, &
-       pamg_nmultigrid, pamg_solver, pamg_levels, pamg_nsmooth, pamg_vtk, pamg_dump_calls
+       pamg_nmultigrid, pamg_solver, pamg_levels, pamg_nsmooth, pamg_vtk, pamg_dump_calls, &
+       pamg_dt, pamg_k, pamg_omega, pamg_ncoarse
 
 contains
 

@@ -2296,7 +2296,7 @@ int pamg_create(const pamg_params *p, pamg_handle **out) {
     if (!p || !out) return PAMG_ERR_ARG;
     *out = nullptr;
     if (p->multi_levels < 1 || p->multi_levels > p->n_split || p->n_split > kMaxLevels || p->n_split < 1 ||
-        p->n_smooth < 0 || p->n_coarse < 0 || (p->solver < 1 || p->solver > 3) || !(p->dt > 0) ||
+        p->n_smooth < 1 || p->n_coarse < 0 || (p->solver < 1 || p->solver > 3) || !(p->dt > 0) ||
         p->theta != 1.0 || (p->halo_mode != 0 && p->halo_mode != 1) ||
         (p->coarse_solver != 0 && p->coarse_solver != 1) || p->fused < 0 || p->fused > 3 ||
         (p->arith != 0 && p->arith != 1) || (p->halo_exchange != 0 && p->halo_exchange != 1) ||

@@ -605,10 +605,13 @@ __global__ __launch_bounds__(kMTc, 3) void k_vc_coarse(VArgs A, const double *__
     stamp<kMTc>(A, 3);
     // ---- phase B: the n_coarse smoother calls of the coarsest level (:351-353) with the
     //      prolongation-leg call (:376) of every other level in its first n_smooth sweeps
+    //      (n_coarse = 0: the coarsest level has no call to interleave with -- the other levels' call runs
+    //      alone; min(ns, nB) as the bound dropped it with the coarsest level's, tests/test_parameters.py P4)
     const int nB = ns * A.n_coarse;
-    for (int it = 0; it < min(ns, nB); ++it) {
+    for (int it = 0; it < ns; ++it) {
 #pragma unroll
         for (int j = 0; j < N; ++j) {
+            if (Q::lev(j) == C && nB == 0) continue;
             ST St;
             stc_of(j, St);
             copy3(p[j], x[j]);

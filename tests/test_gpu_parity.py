@@ -24,7 +24,7 @@ FP64 = [n for n in goldens.names() if not n.endswith("fp32")]
 
 def gpu_solver(meta, **kw):
     mesh = pamg.Mesh.read(os.path.join(goldens.MESHES, meta["mesh"]))
-    args = dict(n_smooth=meta["n_smooth"], solver=meta["solver"])
+    args = dict(n_smooth=meta["n_smooth"], solver=meta["solver"], **goldens.physics(meta))
     args.update(kw)
     return pamg.SemiImplicitIterative(mesh, meta["n_split"], meta["levels"], **args)
 
@@ -72,7 +72,7 @@ def test_each_reference_call_site(name):
             s.copy_to_tnn(l)
             continue
         {"smooth": lambda: s.smoother(l), "restrict": lambda: s.restrictor(l),
-         "residual": lambda: s.get_residual(l), "coarse": lambda: s.smoother(l, 15),
+         "residual": lambda: s.get_residual(l), "coarse": lambda: s.smoother(l, meta.get("n_coarse", 15)),
          "prolong": lambda: s.prolongator(l)}[op]()
         tag = next(tags)
         assert tag.endswith(f"{op}_L{l}")

@@ -18,10 +18,11 @@ TOL = 1e-12
 STATE_KEYS = ("tnew", "told", "RHS", "res")
 
 
-def make_oracle(meta):
+def make_oracle(meta, **kw):
     mesh = O.read_msh(os.path.join(goldens.MESHES, meta["mesh"]))
     return mesh, O.Oracle(mesh, meta["n_split"], meta["levels"], n_smooth=meta["n_smooth"],
-                          solver=meta["solver"], ntime=meta["ntime"], n_multigrid=meta["n_multigrid"])
+                          solver=meta["solver"], ntime=meta["ntime"], n_multigrid=meta["n_multigrid"],
+                          **goldens.physics(meta), **kw)
 
 
 FP64 = [n for n in goldens.names() if not n.endswith("fp32")]
@@ -92,7 +93,7 @@ def _replay_first_cycle(o, meta, d):
         elif op == "residual":
             o.get_residual(l)
         elif op == "coarse":
-            for _ in range(15):
+            for _ in range(meta.get("n_coarse", 15)):
                 o.smoother(l)
         elif op == "prolong":
             o.prolongator(l)
