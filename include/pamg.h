@@ -72,7 +72,10 @@ extern "C" {
 #define PAMG_K_COARSE_GATHER 17  /* op = 1 on a partition: the ranks' coarsest-level blocks (RHS each cycle, tnew once
                                     per call) gathered into every rank's replica of that level (the agglomerated
                                     coarsest level: the single-domain chain runs on each rank) */
-#define PAMG_K_COUNT 18
+#define PAMG_K_NORM 18           /* a reduction pass of pamg_field_norm / pamg_get_convergence (24 B per sub-element) or
+                                    pamg_residual_norm / pamg_solve (tnew and RHS in, no field out: 48 B per
+                                    sub-element + the operator records), with its one-workgroup combine launch */
+#define PAMG_K_COUNT 19
 
 typedef struct pamg_handle pamg_handle;
 typedef struct pamg_mesh pamg_mesh;
@@ -215,6 +218,45 @@ int pamg_set_call_schedule(pamg_handle *h, int schedule);
  *  */
 int pamg_vcycle_flops(pamg_handle *h, double *flops_per_cycle);
 int pamg_synchronize(pamg_handle *h);
+
+/* ---- convergence control ----
+ * Norms are reduced on the device in one pass and a one-workgroup combine launch, deterministically (fixed
+ * reduction tree, no floating-point atomics): the same state gives the same double. A NaN or +-inf among the
+ * reduced values makes every kind return NaN. A level without sub-elements (a rank that owns nothing) reduces
+ * to REF 0, MAXABS 0, L2 0.
+ * Multi-GPU: with nranks > 1 every value is the global one over the owned un_eles of all ranks -- each rank
+ * reduces its own level and the ranks' records are gathered (one ncclAllGather, or the local group's host
+ * slots) and combined in rank order, so the maxima are bitwise the single domain's, the sum is deterministic
+ * for a given owner map, and every rank receives the same double; every rank must make the call. A detached
+ * partition (pamg_comm_init with id == NULL and no local group bound) returns its LOCAL value. */
+#define PAMG_NORM_REF    0  /* the reference's get_convergence: max(0, max_i r_i), signed; its loop starts from 0.0 (:879-887) */
+#define PAMG_NORM_MAXABS 1  /* max_i |r_i| */
+#define PAMG_NORM_L2     2  /* sqrt(sum_i r_i^2) */
+
+/* read-only reduction of a state field (selectors of pamg_get_state); the state is untouched.
+ * PAMG_ERR_ARG on the agglomerated coarsest level of an op = 1 partition (replicated, not partitioned) */
+int pamg_field_norm(pamg_handle *h, int level, int what, int kind, double *value);
+/* `call get_convergence` (:876-889): pamg_get_residual(level), then PAMG_NORM_REF of tracer(level)%residuale.
+ * The state after the call is that after pamg_get_residual(level). */
+int pamg_get_convergence(pamg_handle *h, int level, double *convergence);
+/* the same residual A tnew - RHS reduced without being stored: no field, halo word or host-side flag
+ * (rhsn_valid, overlap_static_l1, tnn_level, ...) changes, so the cycles after it are bitwise those without it
+ * (pamg_get_residual between two cycles of cycle = 0 is not: the next restrictor reads the residual the
+ * previous cycle left, :336-338). op = 0 with solver 1 or 3 only: op = 1's residual first rewrites the halo
+ * words and solver 2's level-1 residual re-assembles the RHS, so neither can be read-only (PAMG_ERR_ARG) */
+int pamg_residual_norm(pamg_handle *h, int level, int kind, double *value);
+/* V-cycles of the handle's configuration in calls of check_every cycles, pamg_residual_norm(1, kind) after each;
+ * stops at the first value <= tol, at max_cycles, or at a non-finite value. After c cycles the state is bitwise
+ * that of the same sequence of pamg_vcycle calls. tol < 0 never stops the run (a monitored run). Check i goes
+ * into history[i] while i < history_len (history may be NULL with history_len 0); *n_history counts all checks.
+ * *cycles, *value (the last check's; NaN if none was made), *status and *n_history may each be NULL. Does not
+ * call pamg_begin_timestep. max_cycles < 0, check_every < 1 or an unknown kind: PAMG_ERR_ARG. On a partition
+ * every rank sees the same values and so issues the same calls. */
+int pamg_solve(pamg_handle *h, int kind, double tol, int max_cycles, int check_every,
+               int *cycles, double *value, int *status, double *history, int history_len, int *n_history);
+#define PAMG_SOLVE_CONVERGED 0
+#define PAMG_SOLVE_MAXCYCLES 1
+#define PAMG_SOLVE_NONFINITE 2
 
 /* ---- measurement ---- */
 /* enable HIP-event timing of the kernel classes in `mask` (bit PAMG_K_*) */

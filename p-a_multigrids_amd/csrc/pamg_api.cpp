@@ -36,12 +36,18 @@ struct LocalGroup {
     std::mutex mu;
     std::condition_variable cv;
     std::vector<Post> ready, done;   // [src * n + dst]
+    // the ranks' reduction records of a norm (norm_meet_local): a slot per rank with the sequence number of
+    // the reduction it belongs to, two sets used alternately (a rank posts reduction q + 2 only after every
+    // rank has posted q + 1, that is after every rank has read q's slots)
+    struct NormSlot { long seq = 0; NormRec rec{}; };
+    std::vector<NormSlot> norm;      // [(seq & 1) * n + rank]
     int refs = 0;
 };
 struct Comm {
     ncclComm_t nccl = nullptr;
     LocalGroup *local = nullptr;
     std::vector<long> seq;           // per peer index (level 1's plan): exchanges completed
+    long norm_seq = 0;               // reductions this rank has taken to the local group
     hipEvent_t ev_ready = nullptr, ev_done = nullptr;
 };
 }  // namespace pamg
@@ -2244,6 +2250,136 @@ int nccl_init(pamg_handle *h, ncclComm_t *out, int nranks, ncclUniqueId uid, int
 
 void nccl_release(ncclComm_t c) { (void)ncclCommDestroy(c); }
 
+// ---- convergence control (pamg_norm.hip) ---------------------------------------
+// A reduction of level l on the handle's stream: a state field, or (field == nullptr) the residual
+// A tnew - RHS computed in registers and not stored. Device scratch: the rank's record, the gathered
+// records (one per rank), the slab of per-workgroup partials. One hipMemcpyAsync into the pinned host
+// buffer and one bounded stream wait; on a partition the ranks' records are combined in rank order.
+NormRec norm_identity() { return NormRec{-HUGE_VAL, 0.0, 0.0, 0ull}; }
+
+NormRec norm_join(const NormRec &a, const NormRec &b) {
+    return NormRec{std::fmax(a.max, b.max), std::fmax(a.maxabs, b.maxabs), a.sumsq + b.sumsq,
+                   a.nonfinite | b.nonfinite};
+}
+
+double norm_value(const NormRec &r, int kind) {
+    if (r.nonfinite) return std::nan("");
+    switch (kind) {
+        case PAMG_NORM_REF: return r.max > 0.0 ? r.max : 0.0;   // get_convergence's loop starts from 0.0 (:879)
+        case PAMG_NORM_MAXABS: return r.maxabs;
+        default: return std::sqrt(r.sumsq);
+    }
+}
+
+bool norm_kind_ok(int kind) { return kind == PAMG_NORM_REF || kind == PAMG_NORM_MAXABS || kind == PAMG_NORM_L2; }
+
+// the local group's gather: this rank's record into its slot, every rank's slot of the same reduction out
+int norm_meet_local(pamg_handle *h, const NormRec &mine, NormRec *all) {
+    Comm &C = *h->comm;
+    LocalGroup &G = *C.local;
+    const int me = h->rank, n = G.n;
+    const long seq = ++C.norm_seq;
+    LocalGroup::NormSlot *box = &G.norm[(size_t)(seq & 1) * n];
+    std::unique_lock<std::mutex> lk(G.mu);
+    box[me].seq = seq;
+    box[me].rec = mine;
+    G.cv.notify_all();
+    for (int r = 0; r < n; ++r) {
+        if (!G.cv.wait_for(lk, std::chrono::seconds(local_timeout_s()), [&] { return box[r].seq >= seq; })) {
+            h->err = "local norm gather: rank " + std::to_string(me) + " timed out waiting for rank " +
+                     std::to_string(r) + "'s record";
+            return PAMG_ERR_COMM;
+        }
+        if (box[r].seq != seq) { h->err = "local norm gather: sequence mismatch"; return PAMG_ERR_COMM; }
+        all[r] = box[r].rec;
+    }
+    return PAMG_OK;
+}
+
+int norm_reduce(pamg_handle *h, int l, const double *field, bool residual_form, NormRec *res) {
+    Level &L = h->lv[l];
+    if (h->comm && !h->comm->nccl && !h->comm->local) {
+        h->err = "norm: the communicator was aborted";
+        return PAMG_ERR_COMM;
+    }
+    const bool rccl = h->comm && h->comm->nccl, local = h->comm && h->comm->local;
+    const int ng = rccl || local ? h->nranks : 1;   // records combined (a detached partition: its own)
+    const size_t nslab = norm_slab_records(L);
+    CHK(ensure_scratch(h, (1 + (size_t)ng + nslab) * sizeof(NormRec)));
+    if (!h->norm_host)
+        HIPCHK(h, hipHostMalloc((void **)&h->norm_host, ((size_t)std::max(h->nranks, 1) + 1) * sizeof(NormRec),
+                                hipHostMallocDefault));
+    NormRec *d_rec = reinterpret_cast<NormRec *>(h->scratch), *d_all = d_rec + 1, *d_slab = d_all + ng;
+    NormRec *host = h->norm_host;
+    const bool empty = L.N == 0;   // a rank that owns nothing: no launch, the identities
+    if (!empty) {
+        Span sp(h, PAMG_K_NORM, residual_form ? 48.0 * (double)L.N + 168.0 * h->U : 24.0 * (double)L.N);
+        if (residual_form) HIPCHK(h, launch_residual_reduce(h->stream, L, 1 / h->p.dt, d_slab, d_rec));
+        else HIPCHK(h, launch_field_reduce(h->stream, L, field, d_slab, d_rec));
+    }
+    if (rccl) {
+        if (empty) {
+            host[ng] = norm_identity();
+            HIPCHK(h, hipMemcpyAsync(d_rec, &host[ng], sizeof(NormRec), hipMemcpyHostToDevice, h->stream));
+        }
+        // one all-gather of the records (4 words each), settled and aborted on failure as a halo exchange is
+        const ncclResult_t r = ncclAllGather(d_rec, d_all, sizeof(NormRec) / sizeof(uint64_t), ncclUint64,
+                                             h->comm->nccl, h->stream);
+        const int rc = nccl_settle(h->comm->nccl, r, local_timeout_s(), h->err, "ncclAllGather (norm)");
+        if (rc != PAMG_OK) {
+            (void)ncclCommAbort(h->comm->nccl);
+            h->comm->nccl = nullptr;
+            return rc;
+        }
+        HIPCHK(h, hipMemcpyAsync(host, d_all, (size_t)ng * sizeof(NormRec), hipMemcpyDeviceToHost, h->stream));
+        CHK(sync_stream(h, h->stream));
+        CHK(comm_error(h));
+    } else {
+        NormRec mine = norm_identity();
+        if (!empty) {
+            HIPCHK(h, hipMemcpyAsync(host, d_rec, sizeof(NormRec), hipMemcpyDeviceToHost, h->stream));
+            CHK(sync_stream(h, h->stream));
+            mine = host[0];
+        }
+        if (local) CHK(norm_meet_local(h, mine, host));
+        else host[0] = mine;
+    }
+    NormRec out = host[0];
+    for (int r = 1; r < ng; ++r) out = norm_join(out, host[r]);
+    *res = out;
+    return PAMG_OK;
+}
+
+// the agglomerated coarsest level of an op = 1 partition is replicated on every rank, not partitioned
+int norm_level_ok(pamg_handle *h, int level) {
+    if (h->agg && level == h->p.multi_levels) {
+        h->err = "norm: the agglomerated coarsest level of an op = 1 partition is replicated, not partitioned";
+        return PAMG_ERR_ARG;
+    }
+    return PAMG_OK;
+}
+
+int residual_norm_ok(pamg_handle *h) {
+    if (h->p.op == 1) {
+        h->err = "residual norm: op = 1's residual first rewrites the halo words, so it cannot be read-only "
+                 "(use pamg_get_convergence)";
+        return PAMG_ERR_ARG;
+    }
+    if (h->p.solver == 2) {
+        h->err = "residual norm: solver 2's level-1 residual re-assembles the RHS, so it cannot be read-only "
+                 "(use pamg_get_convergence)";
+        return PAMG_ERR_ARG;
+    }
+    return PAMG_OK;
+}
+
+int residual_norm(pamg_handle *h, int level, int kind, double *value) {
+    NormRec r;
+    CHK(norm_reduce(h, level, nullptr, true, &r));
+    *value = norm_value(r, kind);
+    return PAMG_OK;
+}
+
 void free_levels(pamg_handle *h) {
     for (int l = 1; l <= kMaxLevels; ++l) {
         Level &L = h->lv[l];
@@ -2417,6 +2553,7 @@ int pamg_comm_local_group(pamg_handle *const *hs, int n) {
     G->n = n;
     G->ready.resize((size_t)n * n);
     G->done.resize((size_t)n * n);
+    G->norm.resize((size_t)2 * n);
     G->refs = n;
     for (int a = 0; a < n; ++a) {
         pamg_handle *h = hs[a];
@@ -2875,6 +3012,73 @@ int pamg_vcycle(pamg_handle *h, int n) {
     return comm_error(h);
 }
 
+int pamg_field_norm(pamg_handle *h, int level, int what, int kind, double *value) {
+    if (!h || !value) return PAMG_ERR_ARG;
+    if (!norm_kind_ok(kind)) { h->err = "norm: unknown kind"; return PAMG_ERR_ARG; }
+    CHK(settle(h));
+    if (what == PAMG_TNEW_NONLIN) level = h->tnn_level;   // as pamg_get_state
+    CHK(check_level(h, level));
+    CHK(norm_level_ok(h, level));
+    const double *src = field_ptr(h, level, what);
+    if (!src) { h->err = "norm: no such field on this level"; return PAMG_ERR_ARG; }
+    NormRec r;
+    CHK(norm_reduce(h, level, src, false, &r));
+    *value = norm_value(r, kind);
+    return PAMG_OK;
+}
+
+int pamg_get_convergence(pamg_handle *h, int level, double *convergence) {
+    if (!h || !convergence) return PAMG_ERR_ARG;
+    CHK(settle(h));
+    CHK(check_level(h, level));
+    CHK(norm_level_ok(h, level));
+    CHK(residual(h, level));   // `call get_residual(ilevel)` (:877)
+    NormRec r;
+    CHK(norm_reduce(h, level, h->lv[level].RES, false, &r));
+    *convergence = norm_value(r, PAMG_NORM_REF);
+    return PAMG_OK;
+}
+
+int pamg_residual_norm(pamg_handle *h, int level, int kind, double *value) {
+    if (!h || !value) return PAMG_ERR_ARG;
+    if (!norm_kind_ok(kind)) { h->err = "norm: unknown kind"; return PAMG_ERR_ARG; }
+    CHK(residual_norm_ok(h));
+    CHK(settle(h));
+    CHK(check_level(h, level));
+    return residual_norm(h, level, kind, value);
+}
+
+int pamg_solve(pamg_handle *h, int kind, double tol, int max_cycles, int check_every, int *cycles, double *value,
+               int *status, double *history, int history_len, int *n_history) {
+    if (!h) return PAMG_ERR_ARG;
+    if (!norm_kind_ok(kind)) { h->err = "solve: unknown kind"; return PAMG_ERR_ARG; }
+    if (max_cycles < 0 || check_every < 1 || history_len < 0 || (history_len > 0 && !history)) {
+        h->err = "solve: max_cycles >= 0, check_every >= 1 and a history array of history_len entries are required";
+        return PAMG_ERR_ARG;
+    }
+    CHK(residual_norm_ok(h));
+    CHK(check_level(h, 1));
+    int done = 0, checks = 0, st = PAMG_SOLVE_MAXCYCLES;
+    double v = std::nan("");
+    while (done < max_cycles) {
+        const int n = std::min(check_every, max_cycles - done);
+        CHK(vcycle(h, n, false));   // pamg_vcycle(n)
+        CHK(comm_error(h));
+        done += n;
+        CHK(settle(h));
+        CHK(residual_norm(h, 1, kind, &v));
+        if (checks < history_len) history[checks] = v;
+        ++checks;
+        if (!std::isfinite(v)) { st = PAMG_SOLVE_NONFINITE; break; }
+        if (v <= tol) { st = PAMG_SOLVE_CONVERGED; break; }
+    }
+    if (cycles) *cycles = done;
+    if (value) *value = v;
+    if (status) *status = st;
+    if (n_history) *n_history = checks;
+    return PAMG_OK;
+}
+
 int pamg_direct_solve(pamg_handle *h, int level) {
     if (!h) return PAMG_ERR_ARG;
     CHK(settle(h));
@@ -3097,6 +3301,7 @@ int pamg_destroy(pamg_handle *h) {
     dev_free(h->chain_tmo);
     if (h->gate) (void)hipFree(h->gate);
     if (h->gate_stat) (void)hipHostFree(h->gate_stat);
+    if (h->norm_host) (void)hipHostFree(h->norm_host);
     if (h->stream_fb) (void)hipStreamDestroy(h->stream_fb);
     dev_free(h->xc_done);
     dev_free(h->xe_done);

@@ -160,7 +160,14 @@ struct Timing {
     double bytes[PAMG_K_COUNT] = {0};
 };
 
-struct Comm;  // pamg_comm.cpp
+struct Comm;  // pamg_api.cpp
+
+// the record one reduction pass over a level produces (pamg_norm.hip): the identities are
+// max = -inf, maxabs = 0, sumsq = 0; nonfinite != 0: some input was NaN or +-inf (fmax drops a NaN)
+struct NormRec {
+    double max, maxabs, sumsq;
+    unsigned long long nonfinite;
+};
 
 }  // namespace pamg
 
@@ -272,6 +279,8 @@ struct pamg_handle {
     bool coarse_only = false;        // this handle is such a replica: levels below L are not allocated
     bool borrowed_stream = false;    // `stream` belongs to another handle (the replica's parent)
     pamg_handle *tparent = nullptr;  // the replica's timing spans and fallback counts go to its parent's Timing
+    // the reductions' read-back (pamg_field_norm, pamg_residual_norm): pinned, one record per rank (on first use)
+    pamg::NormRec *norm_host = nullptr;
 };
 
 // ---- setup (pamg_setup.cpp) ----
@@ -463,6 +472,13 @@ hipError_t launch_face_chain(hipStream_t s, const Level &L, int U, int cus, doub
                              unsigned *flags, const int *nb_off, const int *nb_list, unsigned *tmo, int run, int total,
                              int store, bool rb, bool level1, double rdt, double omega, int slots, bool from_T = false,
                              unsigned f0 = 0, int guard = 0, ChainGate G = ChainGate());
+// ---- reductions (pamg_norm.hip) ----
+// one pass over level L: a partial record per workgroup into slab (norm_slab_records(L) of them), combined
+// by a second, one-workgroup launch into *out; L.N == 0 launches nothing (the caller holds the identities)
+size_t norm_slab_records(const Level &L);
+hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, NormRec *slab, NormRec *out);
+// A tnew - RHS of level L (k_residual's values, bitwise) reduced without being stored
+hipError_t launch_residual_reduce(hipStream_t s, const Level &L, double rdt, NormRec *slab, NormRec *out);
 hipError_t launch_sweep_assembled(hipStream_t s, const Level &L, double *out, double rdt);
 hipError_t launch_sweep_stencil(hipStream_t s, const Level &L, double *out, double rdt);
 }  // namespace pamg

@@ -1,0 +1,195 @@
+// Device reductions of libpamg (gfx950): one pass over a level produces the record
+// {max, maxabs, sumsq, nonfinite} of a state field (k_field_reduce) or of the residual
+// A tnew - RHS computed on the fly (k_residual_reduce), which stores no field: the convergence
+// monitor of pamg_residual_norm / pamg_solve must leave the state untouched (the reference
+// cycle's restrictor reads the residual the previous cycle left, transport_tri_semi.F90:336-338,
+// so a stored residual between two cycles changes the next one).
+//
+// The reduction is deterministic: lanes of a wave are combined with cross-lane shuffles in a
+// fixed butterfly, the waves of a workgroup through LDS in wave order, every workgroup writes
+// one partial record to a slab, and a second launch of one workgroup combines the slab -- each
+// thread its records (every 1024th) in index order, then the same fixed tree. No floating-point
+// atomics and no in-launch hand-off between workgroups: the launch boundary is the ordering.
+// fmax drops a NaN, so non-finite inputs are carried in a separate word; the combine launch
+// writes NaN into the three values when it is set.
+#include <hip/hip_runtime.h>
+
+#include <limits>
+
+#include "pamg_device.h"
+#include "pamg_internal.h"
+
+namespace pamg {
+namespace {
+
+using namespace detail;
+
+constexpr int kWaves = kBlock / 64;
+// the combine launch: one workgroup of 16 waves, 8 records in flight per thread
+constexpr int kCombineBlock = 1024, kCombineWaves = kCombineBlock / 64, kCombineBatch = 8;
+
+__device__ __forceinline__ NormRec rec_identity() {
+    NormRec r;
+    r.max = -__builtin_huge_val();
+    r.maxabs = 0.0;
+    r.sumsq = 0.0;
+    r.nonfinite = 0ull;
+    return r;
+}
+
+// one value into a record; the exponent test also catches what fmax would drop (NaN)
+__device__ __forceinline__ void rec_add(NormRec &r, double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    r.nonfinite |= (unsigned long long)((b & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
+    r.max = fmax(r.max, v);
+    r.maxabs = fmax(r.maxabs, __builtin_fabs(v));
+    r.sumsq = r.sumsq + v * v;
+}
+
+// a (the lower index) combined with b
+__device__ __forceinline__ NormRec rec_join(const NormRec &a, const NormRec &b) {
+    NormRec r;
+    r.max = fmax(a.max, b.max);
+    r.maxabs = fmax(a.maxabs, b.maxabs);
+    r.sumsq = a.sumsq + b.sumsq;
+    r.nonfinite = a.nonfinite | b.nonfinite;
+    return r;
+}
+
+__device__ __forceinline__ NormRec rec_shfl_down(const NormRec &a, int d) {
+    NormRec r;
+    r.max = __shfl_down(a.max, d, 64);
+    r.maxabs = __shfl_down(a.maxabs, d, 64);
+    r.sumsq = __shfl_down(a.sumsq, d, 64);
+    r.nonfinite = __shfl_down(a.nonfinite, d, 64);
+    return r;
+}
+
+// every thread of the workgroup (NW waves) calls it (threads past the tail with the identity); thread 0
+// returns the workgroup's record
+template <int NW = kWaves>
+__device__ __forceinline__ NormRec block_reduce(NormRec r, NormRec *lds) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) r = rec_join(r, rec_shfl_down(r, d));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) lds[wave] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        r = lds[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) r = rec_join(r, lds[w]);
+    }
+    return r;
+}
+
+// one state field: one thread per pair of sub-elements, 24 B per sub-element in, one record per workgroup out
+__global__ __launch_bounds__(kBlock) void k_field_reduce(const double *__restrict__ F, int64_t pitch, int64_t npairs,
+                                                         NormRec *__restrict__ slab) {
+    __shared__ NormRec lds[kWaves];
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    NormRec r = rec_identity();
+    if (p < npairs) {
+        const int64_t s = 2 * p;
+        double2 v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = ld2(F + c * pitch + s);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec_add(r, v[c].x);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec_add(r, v[c].y);
+    }
+    r = block_reduce(r, lds);
+    if (threadIdx.x == 0) slab[blockIdx.x] = r;
+}
+
+// get_residual's A tnew - RHS (:725-873) reduced in registers: k_residual's loads and its resid(), so
+// every value is bitwise the one k_residual would store; 48 B per sub-element in, no field out
+template <class ST>
+__global__ __launch_bounds__(kBlock) void k_residual_reduce(const double *__restrict__ T,
+                                                            const double *__restrict__ RHS,
+                                                            const double *__restrict__ stc, int64_t pitch,
+                                                            int64_t npairs, int nsub_log2, double rdt,
+                                                            NormRec *__restrict__ slab) {
+    __shared__ NormRec lds[kWaves];
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    NormRec r = rec_identity();
+    if (p < npairs) {
+        const int64_t s = 2 * p;
+        double2 xv[3], bv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            xv[c] = ld2(T + c * pitch + s);
+            bv[c] = ld2(RHS + c * pitch + s);
+        }
+        ST S;
+        load_stc(stc + (s >> nsub_log2) * kStcStride, S);
+        const double x0[3] = {xv[0].x, xv[1].x, xv[2].x}, x1[3] = {xv[0].y, xv[1].y, xv[2].y};
+        const double b0[3] = {bv[0].x, bv[1].x, bv[2].x}, b1[3] = {bv[0].y, bv[1].y, bv[2].y};
+        double r0[3], r1[3];
+        resid(S, rdt, x0, b0, r0);
+        resid(S, rdt, x1, b1, r1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec_add(r, r0[c]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec_add(r, r1[c]);
+    }
+    r = block_reduce(r, lds);
+    if (threadIdx.x == 0) slab[blockIdx.x] = r;
+}
+
+// the slab's n records into *out, one workgroup of 1024 threads: thread t takes the records t, t + 1024,
+// t + 2048, ... in index order, then the workgroup's fixed tree. The loads of a batch of 8 records are
+// issued before any is joined: with one load in flight per thread (256 threads, 64 records each, one
+// after the other) the launch took 21.6 us for the bench shape's 16,384 records, 64 memory latencies in a row
+__global__ __launch_bounds__(kCombineBlock) void k_norm_combine(const NormRec *__restrict__ slab, int n,
+                                                                NormRec *__restrict__ out) {
+    __shared__ NormRec lds[kCombineWaves];
+    NormRec r = rec_identity();
+    int i = threadIdx.x;
+    for (; i + (kCombineBatch - 1) * kCombineBlock < n; i += kCombineBatch * kCombineBlock) {
+        NormRec v[kCombineBatch];
+#pragma unroll
+        for (int q = 0; q < kCombineBatch; ++q) v[q] = slab[i + q * kCombineBlock];
+#pragma unroll
+        for (int q = 0; q < kCombineBatch; ++q) r = rec_join(r, v[q]);
+    }
+    for (; i < n; i += kCombineBlock) r = rec_join(r, slab[i]);
+    r = block_reduce<kCombineWaves>(r, lds);
+    if (threadIdx.x == 0) {
+        if (r.nonfinite) r.max = r.maxabs = r.sumsq = __builtin_nan("");
+        *out = r;
+    }
+}
+
+inline unsigned grid_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+inline int log2i(int v) { int r = 0; while ((1 << r) < v) ++r; return r; }
+
+}  // namespace
+
+size_t norm_slab_records(const Level &L) { return (size_t)grid_for(L.N / 2); }
+
+hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, NormRec *slab, NormRec *out) {
+    const int64_t npairs = L.N / 2;
+    if (npairs == 0) return hipSuccess;   // the caller supplies the identities
+    const unsigned g = grid_for(npairs);
+    hipLaunchKernelGGL(k_field_reduce, dim3(g), dim3(kBlock), 0, s, field, L.pitch, npairs, slab);
+    hipLaunchKernelGGL(k_norm_combine, dim3(1), dim3(kCombineBlock), 0, s, slab, (int)g, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_residual_reduce(hipStream_t s, const Level &L, double rdt, NormRec *slab, NormRec *out) {
+    const int64_t npairs = L.N / 2;
+    if (npairs == 0) return hipSuccess;
+    const unsigned g = grid_for(npairs);
+    const int lg = log2i(L.nsub);
+    if (L.arith == 1)
+        hipLaunchKernelGGL((k_residual_reduce<StcF>), dim3(g), dim3(kBlock), 0, s, L.T, L.RHS, L.stc, L.pitch, npairs,
+                           lg, rdt, slab);
+    else
+        hipLaunchKernelGGL((k_residual_reduce<Stc>), dim3(g), dim3(kBlock), 0, s, L.T, L.RHS, L.stc, L.pitch, npairs,
+                           lg, rdt, slab);
+    hipLaunchKernelGGL(k_norm_combine, dim3(1), dim3(kCombineBlock), 0, s, slab, (int)g, out);
+    return hipGetLastError();
+}
+
+}  // namespace pamg

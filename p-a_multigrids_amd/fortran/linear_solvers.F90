@@ -27,7 +27,7 @@ module LinearSolvers
   integer, save :: bound_U = -1, bound_split = 0, bound_levels = 0
 
   public :: pamg_bind_mesh, pamg_bind_handle, pamg_bound_handle, pamg_get_fields, pamg_get_tnew_nonlin
-  public :: GSsolver_MeshCC, GSsolver_MeshSD, GSsolver_MeshMix
+  public :: GSsolver_MeshCC, GSsolver_MeshSD, GSsolver_MeshMix, get_convergence
 
 contains
 
@@ -179,6 +179,18 @@ contains
     call get_one(PAMG_TNEW_NONLIN, level, buf)
     tnn = reshape(buf, [3, nsub, bound_U])
   end subroutine pamg_get_tnew_nonlin
+
+  ! the reference's get_convergence (transport_tri_semi.F90:876-889; its call site :354-358 is commented
+  ! out): get_residual on ilevel, then its `convergence` variable = max(0, max residuale), reduced on the
+  ! device. There it is an internal routine reading ilevel and writing convergence by host association; here
+  ! both are arguments.
+  subroutine get_convergence(ilevel, convergence)
+    integer, intent(in) :: ilevel
+    real, intent(out) :: convergence
+    real(c_double) :: v
+    call pamg_check(pamg_get_convergence(bound, int(ilevel, c_int), v), bound, 'pamg_get_convergence')
+    convergence = v
+  end subroutine get_convergence
 
   subroutine get_one(what, level, buf)
     integer(c_int), intent(in) :: what

@@ -13,6 +13,9 @@ module pamg
   integer(c_int), parameter, public :: PAMG_OK = 0
   integer(c_int), parameter, public :: PAMG_TNEW = 0, PAMG_TOLD = 1, PAMG_RHS = 2, PAMG_RESIDUAL = 3
   integer(c_int), parameter, public :: PAMG_TNEW_NONLIN = 4, PAMG_SOURCE = 5
+  ! kinds of the norms and pamg_solve's status (include/pamg.h)
+  integer(c_int), parameter, public :: PAMG_NORM_REF = 0, PAMG_NORM_MAXABS = 1, PAMG_NORM_L2 = 2
+  integer(c_int), parameter, public :: PAMG_SOLVE_CONVERGED = 0, PAMG_SOLVE_MAXCYCLES = 1, PAMG_SOLVE_NONFINITE = 2
 
   type, bind(C), public :: pamg_params
     integer(c_int) :: n_split, multi_levels, n_smooth, n_coarse, solver, device
@@ -33,6 +36,7 @@ module pamg
   public :: pamg_get_residual, pamg_prolongator, pamg_vcycle, pamg_run, pamg_synchronize
   public :: pamg_destroy, pamg_last_error, pamg_check, c_path, pamg_block_inverse, pamg_direct_solve
   public :: pamg_write_vtu, pamg_csr_create, pamg_csr_mul_array, pamg_csr_free, pamg_tnn_level
+  public :: pamg_field_norm, pamg_get_convergence, pamg_residual_norm, pamg_solve
 
   interface
     subroutine pamg_default_params(p) bind(C, name='pamg_default_params')
@@ -126,6 +130,35 @@ module pamg
       import :: c_int, c_ptr
       type(c_ptr), value :: h
       integer(c_int), value :: n
+    end function
+    ! convergence control: get_convergence (transport_tri_semi.F90:876-889) and the read-only monitor
+    integer(c_int) function pamg_field_norm(h, level, what, kind, value) bind(C, name='pamg_field_norm')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: level, what, kind
+      real(c_double), intent(out) :: value
+    end function
+    integer(c_int) function pamg_get_convergence(h, level, convergence) bind(C, name='pamg_get_convergence')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: level
+      real(c_double), intent(out) :: convergence
+    end function
+    integer(c_int) function pamg_residual_norm(h, level, kind, value) bind(C, name='pamg_residual_norm')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: level, kind
+      real(c_double), intent(out) :: value
+    end function
+    integer(c_int) function pamg_solve(h, kind, tol, max_cycles, check_every, cycles, value, status, history, &
+                                       history_len, n_history) bind(C, name='pamg_solve')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: kind, max_cycles, check_every, history_len
+      real(c_double), value :: tol
+      integer(c_int), intent(out) :: cycles, status, n_history
+      real(c_double), intent(out) :: value
+      real(c_double), intent(inout) :: history(*)
     end function
     integer(c_int) function pamg_run(h, ntime, n_multigrid) bind(C, name='pamg_run')
       import :: c_int, c_ptr

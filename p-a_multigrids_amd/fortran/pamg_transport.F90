@@ -16,6 +16,10 @@
 ! vtk_interval > 0 writes Tracer_<itime>.vtu at the start of every vtk_interval-th
 ! step as the reference's get_vtu call site does (:301-311; main.F90:46 passes 1),
 ! through pamg_write_vtu (full precision, raw appended binary).
+! solve_tol >= 0 with call_sites=0: every time step is pamg_begin_timestep followed by pamg_solve --
+! V-cycles in calls of check_every (default 1) cycles until max |A tnew - RHS| of level 1 is <= solve_tol
+! or n_multigrid cycles have run -- and prints `convergence` and the cycle count. The default
+! solve_tol = -1.0 leaves the run as it was.
 program pamg_transport
   use iso_c_binding
   use pamg
@@ -28,8 +32,12 @@ program pamg_transport
   integer :: n_split = 1, multi_levels = 1, n_smooth = 4, solver = 3, ntime = 2, n_multigrid = 2
   integer :: device = 0, call_sites = 1, facade_sweeps = 0, vtk_interval = 0, vtk_io, cycle = 0
   character(len=64) :: vtu_name
+  real(c_double) :: solve_tol = -1.0_c_double, convergence
+  integer :: check_every = 1
+  integer(c_int) :: solve_cycles, solve_status, solve_checks
+  real(c_double) :: solve_history(1)
   namelist /transport/ mesh_file, n_split, multi_levels, n_smooth, solver, ntime, n_multigrid, device, dump, &
-       call_sites, facade_sweeps, vtk_interval, cycle
+       call_sites, facade_sweeps, vtk_interval, cycle, solve_tol, check_every
 
   character(len=512) :: cfg
   type(c_ptr) :: m = c_null_ptr, h = c_null_ptr
@@ -89,7 +97,15 @@ program pamg_transport
   print *, '---------------------------------------------------------'
   call system_clock(c0, crate)
 
-  if (call_sites == 0) then
+  if (call_sites == 0 .and. solve_tol >= 0.0_c_double) then
+    do itime = 1, ntime
+      call pamg_check(pamg_begin_timestep(h), h, 'begin_timestep')     ! :316-317
+      call pamg_check(pamg_solve(h, PAMG_NORM_MAXABS, solve_tol, int(n_multigrid, c_int), int(check_every, c_int), &
+                                 solve_cycles, convergence, solve_status, solve_history, 0_c_int, solve_checks), &
+                      h, 'pamg_solve')
+      print *, 'semi', itime, ' convergence', convergence, ' cycles', solve_cycles, ' status', solve_status
+    end do
+  else if (call_sites == 0) then
     call pamg_check(pamg_run(h, int(ntime, c_int), int(n_multigrid, c_int)), h, 'pamg_run')
   else
     vtk_io = vtk_interval                                   ! :132

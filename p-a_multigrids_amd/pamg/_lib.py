@@ -22,7 +22,12 @@ TNEW, TOLD, RHS, RESIDUAL, TNEW_NONLIN, SOURCE = 0, 1, 2, 3, 4, 5
  K_VCYCLE_COARSE) = range(10)
 K_NAMES = ["smooth_L1", "smooth", "residual", "restrict", "prolong", "rhs", "halo", "sweep_bench", "vcycle",
            "vcycle_coarse", "vcycle_pipe", "vcycle_rhsf", "vcycle_res", "vcycle_res_rhsf", "vcycle_corr",
-           "halo_early", "face_fallback", "coarse_gather"]
+           "halo_early", "face_fallback", "coarse_gather", "norm"]
+K_NORM = K_NAMES.index("norm")
+# kinds of pamg_field_norm / pamg_residual_norm / pamg_solve (PAMG_NORM_REF, PAMG_NORM_MAXABS, PAMG_NORM_L2)
+NORM_REF, NORM_MAXABS, NORM_L2 = 0, 1, 2
+# pamg_solve's status (PAMG_SOLVE_CONVERGED, PAMG_SOLVE_MAXCYCLES, PAMG_SOLVE_NONFINITE)
+SOLVE_CONVERGED, SOLVE_MAXCYCLES, SOLVE_NONFINITE = 0, 1, 2
 
 
 class PamgParams(C.Structure):
@@ -81,6 +86,10 @@ def lib():
         "pamg_vcycle": (I, [P, I]),
         "pamg_run": (I, [P, I, I]),
         "pamg_synchronize": (I, [P]),
+        "pamg_field_norm": (I, [P, I, I, I, C.POINTER(D)]),
+        "pamg_get_convergence": (I, [P, I, C.POINTER(D)]),
+        "pamg_residual_norm": (I, [P, I, I, C.POINTER(D)]),
+        "pamg_solve": (I, [P, I, D, I, I, C.POINTER(I), C.POINTER(D), C.POINTER(I), C.c_void_p, I, C.POINTER(I)]),
         "pamg_timing_enable": (I, [P, C.c_uint]),
         "pamg_timing_reset": (I, [P]),
         "pamg_timing_stride": (I, [P, I]),

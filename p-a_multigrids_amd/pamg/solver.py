@@ -11,7 +11,8 @@ import os
 
 import numpy as np
 
-from ._lib import (PAMG_OK, PamgError, PamgParams, TNEW, TOLD, RHS, RESIDUAL, TNEW_NONLIN, K_NAMES, lib)
+from ._lib import (PAMG_OK, PamgError, PamgParams, TNEW, TOLD, RHS, RESIDUAL, TNEW_NONLIN, K_NAMES, NORM_REF,
+                   NORM_MAXABS, lib)
 
 
 def _check(fn, rc, h=None):
@@ -190,6 +191,38 @@ class SemiImplicitIterative:
     def prolongator(self, level): self._call("pamg_prolongator", level)
     def vcycle(self, n=1): self._call("pamg_vcycle", n)
     def direct_solve(self, level): self._call("pamg_direct_solve", level)
+
+    # ---- convergence control ----------------------------------------------
+    def field_norm(self, what, level=1, kind=NORM_MAXABS):
+        """read-only device reduction of a state field (pamg_field_norm): NORM_REF max(0, max), NORM_MAXABS
+        max |.|, NORM_L2 sqrt(sum of squares); the global value on a bound partition"""
+        v = C.c_double()
+        self._call("pamg_field_norm", level, what, kind, C.byref(v))
+        return v.value
+
+    def get_convergence(self, level=1):
+        """the reference's get_convergence (transport_tri_semi.F90:876-889): get_residual(level), then
+        max(0, max residuale); the state afterwards is that after get_residual(level)"""
+        v = C.c_double()
+        self._call("pamg_get_convergence", level, C.byref(v))
+        return v.value
+
+    def residual_norm(self, level=1, kind=NORM_MAXABS):
+        """the residual A tnew - RHS of `level` reduced without being stored: the state is untouched
+        (pamg_residual_norm; op 0, solver 1 or 3)"""
+        v = C.c_double()
+        self._call("pamg_residual_norm", level, kind, C.byref(v))
+        return v.value
+
+    def solve(self, tol, max_cycles, check_every=1, kind=NORM_MAXABS):
+        """V-cycles in calls of check_every cycles with residual_norm(1, kind) after each, until the value is
+        <= tol (tol < 0: never), max_cycles or a non-finite value (pamg_solve); the caller begins the time
+        step. Returns (cycles, value, status, history) with every check's value in history."""
+        cyc, st, v, n_hist = C.c_int(), C.c_int(), C.c_double(), C.c_int()
+        history = np.zeros(max(0, max_cycles) // max(1, check_every) + 1, np.float64)
+        self._call("pamg_solve", kind, float(tol), max_cycles, check_every, C.byref(cyc), C.byref(v), C.byref(st),
+                   history.ctypes.data, history.size, C.byref(n_hist))
+        return cyc.value, v.value, st.value, [float(x) for x in history[:n_hist.value]]
 
     def write_vtu(self, path, ascii=False):
         """get_vtu (get_vtk_files.F90:10-165) of the level-1 solution at full precision."""
