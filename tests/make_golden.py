@@ -68,6 +68,13 @@ CASES = {
     # n_coarse = 0 with a level between the finest and the coarsest: that level's prolongation-leg call has no
     # coarsest-level call beside it (the two-launch fused form once dropped it with them)
     "u8_s3_l3_nc0":              ("untitled8.msh", 3, 3, 4, 3, 2, 2, 0, "fp64", None, dict(P1, n_coarse=0)),
+    # renumbered variants of three fixtures (tests/mesh_variants.py VARIANTS: the same triangles, node triples
+    # rotated / swapped, another triangle order): together they show all 18 (face, fNeig, Dir) triples of an
+    # interior face, four of which -- (1,1,1), (1,2,0), (2,1,0), (3,3,1) -- no other mesh here has; they pin
+    # update_overlaps' slot arithmetic and t_overlap on those to the reference
+    "u8rn_s3_l3_gs":             ("untitled8_rn.msh", 3, 3, 4, 3, 2, 2, 1, "fp64", None),
+    "irregularrn_s3_l3_jacobi_p1": ("irregular_rn.msh", 3, 3, 4, 1, 2, 2, 0, "fp64", None, P1),
+    "sn2rn_s3_l2_gs":            ("test_sn2_rn.msh", 3, 2, 4, 3, 2, 2, 0, "fp64", None),
 }
 
 
