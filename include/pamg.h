@@ -74,7 +74,10 @@ extern "C" {
                                     coarsest level: the single-domain chain runs on each rank) */
 #define PAMG_K_NORM 18           /* a reduction pass of pamg_field_norm / pamg_get_convergence (24 B per sub-element) or
                                     pamg_residual_norm / pamg_solve (tnew and RHS in, no field out: 48 B per
-                                    sub-element + the operator records), with its one-workgroup combine launch */
+                                    sub-element + the operator records), with its one-workgroup combine launch;
+                                    op = 1 (monitor = 1): the monitor words launch, their exchange between the
+                                    ranks, the reduction and the combine as one span (+ the face records and
+                                    the words) */
 #define PAMG_K_COUNT 19
 
 typedef struct pamg_handle pamg_handle;
@@ -138,7 +141,13 @@ typedef struct {
                          solver 3, Jacobi for solver 1; per-step kernels; no reference output exists (the
                          reference cannot run the block), pinned to the oracle's restatement.
                          Not with solver 2 or coarse_solver 1 */
-    int reserved[1];
+    int monitor;      /* 0 (default): op = 1 has no read-only residual (pamg_residual_norm / pamg_solve refuse it);
+                         1: the handle keeps a monitor halo image of its own (allocated on the first check, the
+                         size of t_overlap) -- a check writes level's tnew words into it (exchanged between the
+                         ranks on every check, 3 words per remote entry through buffers of its own) and reduces
+                         A tnew - RHS from it, so pamg_residual_norm and pamg_solve accept op = 1 and still leave
+                         every field, t_overlap / t_overlap_old, the exchange buffers and the host-side flags as
+                         they were. No effect with op = 0. Any other value: PAMG_ERR_ARG */
 } pamg_params;
 
 /* mode-9 defaults of the reference (main.F90:46-47, transport_tri_semi.F90:117-140) */
@@ -242,8 +251,13 @@ int pamg_get_convergence(pamg_handle *h, int level, double *convergence);
 /* the same residual A tnew - RHS reduced without being stored: no field, halo word or host-side flag
  * (rhsn_valid, overlap_static_l1, tnn_level, ...) changes, so the cycles after it are bitwise those without it
  * (pamg_get_residual between two cycles of cycle = 0 is not: the next restrictor reads the residual the
- * previous cycle left, :336-338). op = 0 with solver 1 or 3 only: op = 1's residual first rewrites the halo
- * words and solver 2's level-1 residual re-assembles the RHS, so neither can be read-only (PAMG_ERR_ARG) */
+ * previous cycle left, :336-338). Solver 1 or 3 only: solver 2's level-1 residual re-assembles the RHS, so it
+ * cannot be read-only (PAMG_ERR_ARG). op = 1 needs pamg_params.monitor = 1: its residual first rewrites the halo
+ * words, so without the handle's monitor image it cannot be read-only either (PAMG_ERR_ARG). With it every
+ * reduced value is bitwise the one pamg_get_residual(level) would store (the values across un_ele faces from
+ * the neighbours' current tnew, other ranks' included: every rank must call). PAMG_ERR_ARG on the agglomerated
+ * coarsest level of an op = 1 partition; PAMG_ERR_STATE for op = 1 on a detached partition, which cannot see
+ * its peers' tnew */
 int pamg_residual_norm(pamg_handle *h, int level, int kind, double *value);
 /* V-cycles of the handle's configuration in calls of check_every cycles, pamg_residual_norm(1, kind) after each;
  * stops at the first value <= tol, at max_cycles, or at a non-finite value. After c cycles the state is bitwise
@@ -251,7 +265,8 @@ int pamg_residual_norm(pamg_handle *h, int level, int kind, double *value);
  * into history[i] while i < history_len (history may be NULL with history_len 0); *n_history counts all checks.
  * *cycles, *value (the last check's; NaN if none was made), *status and *n_history may each be NULL. Does not
  * call pamg_begin_timestep. max_cycles < 0, check_every < 1 or an unknown kind: PAMG_ERR_ARG. On a partition
- * every rank sees the same values and so issues the same calls. */
+ * every rank sees the same values and so issues the same calls. op = 1 needs pamg_params.monitor = 1 (as
+ * pamg_residual_norm). */
 int pamg_solve(pamg_handle *h, int kind, double tol, int max_cycles, int check_every,
                int *cycles, double *value, int *status, double *history, int history_len, int *n_history);
 #define PAMG_SOLVE_CONVERGED 0

@@ -2296,23 +2296,85 @@ int norm_meet_local(pamg_handle *h, const NormRec &mine, NormRec *all) {
     return PAMG_OK;
 }
 
+// ---- the face operator's convergence monitor (pamg_params.monitor = 1, op = 1) ----
+// the monitor's image (t_overlap's size) and the send / receive words of its exchange, 3 per entry, sized for
+// the largest level's plan; on the first check
+int monitor_setup(pamg_handle *h) {
+    if (h->mon_img) return PAMG_OK;
+    size_t ns = 0, nr = 0;
+    for (int l = 1; l <= h->p.multi_levels; ++l) {
+        ns = std::max(ns, h->lv[l].halo.remote.size());
+        nr = std::max(nr, h->lv[l].halo.recv_dst.size());
+    }
+    const size_t n = (size_t)h->slots * 3 * std::max(h->U, 1);
+    double *img = nullptr, *snd = nullptr, *rcv = nullptr;
+    if (dev_alloc(h, &img, n) != PAMG_OK || dev_alloc(h, &snd, 3 * ns) != PAMG_OK ||
+        dev_alloc(h, &rcv, 3 * nr) != PAMG_OK) {
+        dev_free(img); dev_free(snd); dev_free(rcv);
+        return PAMG_ERR_HIP;
+    }
+    h->mon_img = img; h->mon_send = snd; h->mon_recv = rcv;
+    HIPCHK(h, hipMemsetAsync(img, 0, n * sizeof(double), h->stream));
+    return PAMG_OK;
+}
+
+// the monitor words of level l that face un_eles of other ranks: exchange_ring's exchange (3 words per entry) of
+// the monitor's own send words into its own receive words on the handle's stream, unpacked into its image
+int monitor_exchange(pamg_handle *h, int l) {
+    Level &L = h->lv[l];
+    const HaloPlan &P = L.halo;
+    if (!h->comm || P.peers.empty()) return PAMG_OK;
+    hipStream_t st = h->stream;
+    if (h->comm->local) {
+        CHK(exchange_local(h, l, h->mon_send, st, 3, h->mon_recv));
+    } else {
+        NCCLCHK(h, ncclGroupStart());
+        for (size_t q = 0; q < P.peers.size(); ++q) {
+            const int peer = P.peers[q];
+            const size_t ns = (size_t)(P.send_peer_off[q + 1] - P.send_peer_off[q]);
+            const size_t nr = (size_t)(P.recv_peer_off[q + 1] - P.recv_peer_off[q]);
+            if (ns) NCCLQ(h, ncclSend(h->mon_send + 3 * (size_t)P.send_peer_off[q], 3 * ns, ncclDouble, peer,
+                                      h->comm->nccl, st));
+            if (nr) NCCLQ(h, ncclRecv(h->mon_recv + 3 * (size_t)P.recv_peer_off[q], 3 * nr, ncclDouble, peer,
+                                      h->comm->nccl, st));
+        }
+        CHK(nccl_group_end(h));
+    }
+    HIPCHK(h, launch_halo_unpack3(st, L, h->mon_img, h->mon_recv));
+    return PAMG_OK;
+}
+
+// residual_form with op = 1: the face form -- the monitor words of the level, their exchange, then the
+// reduction of the face operator's residual from the monitor's image
 int norm_reduce(pamg_handle *h, int l, const double *field, bool residual_form, NormRec *res) {
     Level &L = h->lv[l];
+    const bool face = residual_form && h->p.op == 1;
     if (h->comm && !h->comm->nccl && !h->comm->local) {
         h->err = "norm: the communicator was aborted";
         return PAMG_ERR_COMM;
     }
     const bool rccl = h->comm && h->comm->nccl, local = h->comm && h->comm->local;
     const int ng = rccl || local ? h->nranks : 1;   // records combined (a detached partition: its own)
-    const size_t nslab = norm_slab_records(L);
+    const size_t nslab = face ? face_norm_slab_records(L) : norm_slab_records(L);
     CHK(ensure_scratch(h, (1 + (size_t)ng + nslab) * sizeof(NormRec)));
+    if (face) CHK(monitor_setup(h));
     if (!h->norm_host)
         HIPCHK(h, hipHostMalloc((void **)&h->norm_host, ((size_t)std::max(h->nranks, 1) + 1) * sizeof(NormRec),
                                 hipHostMallocDefault));
     NormRec *d_rec = reinterpret_cast<NormRec *>(h->scratch), *d_all = d_rec + 1, *d_slab = d_all + ng;
     NormRec *host = h->norm_host;
     const bool empty = L.N == 0;   // a rank that owns nothing: no launch, the identities
-    if (!empty) {
+    if (face) {
+        // tnew and RHS in, the operator (168 B), face (8 kFaceStride) and selector (16 B) records, the words read
+        // and written (24 B each way per boundary position), the exchanged words (24 B out, 24 B in); an empty
+        // rank launches nothing but still meets its peers in the exchange (it has none) and in the gather
+        const HaloPlan &P = L.halo;
+        Span sp(h, PAMG_K_NORM, 48.0 * (double)L.N + (168.0 + 8.0 * kFaceStride + 16.0) * h->U +
+                                    48.0 * (double)h->U * P.nbpos + 24.0 * (double)(P.remote.size() + P.recv_dst.size()));
+        HIPCHK(h, launch_face_monitor_words(h->stream, L, h->U, h->mon_img, h->mon_send));
+        CHK(monitor_exchange(h, l));
+        HIPCHK(h, launch_face_residual_reduce(h->stream, L, h->mon_img, l == 1, 1 / h->p.dt, h->slots, d_slab, d_rec));
+    } else if (!empty) {
         Span sp(h, PAMG_K_NORM, residual_form ? 48.0 * (double)L.N + 168.0 * h->U : 24.0 * (double)L.N);
         if (residual_form) HIPCHK(h, launch_residual_reduce(h->stream, L, 1 / h->p.dt, d_slab, d_rec));
         else HIPCHK(h, launch_field_reduce(h->stream, L, field, d_slab, d_rec));
@@ -2360,15 +2422,20 @@ int norm_level_ok(pamg_handle *h, int level) {
 }
 
 int residual_norm_ok(pamg_handle *h) {
-    if (h->p.op == 1) {
+    if (h->p.op == 1 && h->p.monitor != 1) {
         h->err = "residual norm: op = 1's residual first rewrites the halo words, so it cannot be read-only "
-                 "(use pamg_get_convergence)";
+                 "(use pamg_get_convergence, or create the handle with monitor = 1)";
         return PAMG_ERR_ARG;
     }
     if (h->p.solver == 2) {
         h->err = "residual norm: solver 2's level-1 residual re-assembles the RHS, so it cannot be read-only "
                  "(use pamg_get_convergence)";
         return PAMG_ERR_ARG;
+    }
+    if (h->p.op == 1 && h->nranks > 1 && !h->comm) {
+        h->err = "residual norm: a detached partition (no transport bound) cannot see its peers' tnew, which "
+                 "op = 1's residual reads across the un_ele faces";
+        return PAMG_ERR_STATE;
     }
     return PAMG_OK;
 }
@@ -2403,6 +2470,8 @@ void free_levels(pamg_handle *h) {
     dev_free(h->xe_map);
     h->xe_map = nullptr;
     h->xe_nremote = -1;
+    dev_free(h->mon_img); dev_free(h->mon_send); dev_free(h->mon_recv);
+    h->mon_img = h->mon_send = h->mon_recv = nullptr;
     h->mesh_ready = false;
 }
 
@@ -2437,7 +2506,7 @@ int pamg_create(const pamg_params *p, pamg_handle **out) {
         (p->coarse_solver != 0 && p->coarse_solver != 1) || p->fused < 0 || p->fused > 3 ||
         (p->arith != 0 && p->arith != 1) || (p->halo_exchange != 0 && p->halo_exchange != 1) ||
         (p->cycle != 0 && p->cycle != 1) || (p->cycle == 1 && p->solver == 2) || (p->op != 0 && p->op != 1) ||
-        (p->op == 1 && (p->solver == 2 || p->coarse_solver == 1)))
+        (p->op == 1 && (p->solver == 2 || p->coarse_solver == 1)) || (p->monitor != 0 && p->monitor != 1))
         return PAMG_ERR_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PAMG_ERR_NODEV;
@@ -3045,6 +3114,7 @@ int pamg_residual_norm(pamg_handle *h, int level, int kind, double *value) {
     CHK(residual_norm_ok(h));
     CHK(settle(h));
     CHK(check_level(h, level));
+    CHK(norm_level_ok(h, level));
     return residual_norm(h, level, kind, value);
 }
 

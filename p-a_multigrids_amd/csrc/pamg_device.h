@@ -255,6 +255,34 @@ __device__ __forceinline__ void halo_face(const HaloArgs &H, int4 rec, int f, in
     }
 }
 
+// halo_face's tnew-side words for the convergence monitor (pamg_params.monitor, pamg_face.hip
+// k_face_monitor_words): the same slots -- the index arithmetic of the three modes is halo_face's, line for line
+// (folding the two into shared helpers changed the register allocation of the resident V-cycle kernels, whose
+// code is to stay as it is; tests/test_convergence_face.py holds the two bitwise equal on every (face, fNeig,
+// Dir) triple) -- in an image and a send buffer of the monitor's own (H.tov, H.send; 3 words per send entry: no
+// told half). The boundary values go into the own column of the image as halo_face writes them into t_overlap.
+// Nothing of t_overlap_old, the told halo or the exchange's send buffer is touched (H.tovo and H.told are not
+// read).
+__device__ __forceinline__ void halo_face_monitor(const HaloArgs &H, int4 rec, int f, int i, const double t[3]) {
+    const int mode = rec.x & 3;
+    if (mode == 0) {
+        const int a = (i - 1) * 3 + (f == 3 ? 1 : 0);
+        const int b = (i - 1) * 3 + (f == 2 ? 1 : 2);
+        const double2 v = H.bcv[rec.z + i - 1];
+        H.tov[rec.y + a] = v.x;
+        H.tov[rec.y + b] = v.y;
+    } else if (mode == 1) {
+        const int k = (rec.x >> 2) ? (H.m - i + 1) : i;
+        const int64_t d = rec.y + (int64_t)(k - 1) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) H.tov[d + c] = t[c];
+    } else {
+        double *o = H.send + 3 * (int64_t)(rec.z + i - 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = t[c];
+    }
+}
+
 struct HaloPre {
     int4 hs0, hs1;              // face positions of the two sub-elements
     int4 r1, r2, r3;            // face records (faces 1, 2, 3) of the un_ele

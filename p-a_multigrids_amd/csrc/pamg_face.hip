@@ -24,6 +24,7 @@
 
 #include "pamg_device.h"
 #include "pamg_internal.h"
+#include "pamg_norm_device.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -86,6 +87,26 @@ __global__ __launch_bounds__(kBlock) void k_face_words(const double *__restrict_
     if (P.hs0.x) halo_face<true, true>(H, P.r1, 1, P.hs0.x, t, to);
     if (P.hs0.y) halo_face<true, true>(H, P.r2, 2, P.hs0.y, t, to);
     if (P.hs0.z) halo_face<true, true>(H, P.r3, 3, P.hs0.z, t, to);
+}
+
+// the convergence monitor's words (pamg_params.monitor): k_face_words' work list and loads of tnew, the tnew-side
+// words only, through halo_face_monitor into the monitor's own image and 3-word send buffer (H.tov, H.send) --
+// no t_overlap_old word, no word of the exchange's send buffer, no told read
+__global__ __launch_bounds__(kBlock) void k_face_monitor_words(const double *__restrict__ T, int64_t pitch, HaloArgs H,
+                                                               const int *__restrict__ bpos, int nb, int64_t nwork,
+                                                               int nsub_log2) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nwork) return;
+    const int64_t u = i / nb;
+    const int p = bpos[i - u * nb];
+    const int64_t s = (u << nsub_log2) + p;
+    const int4 hs = H.hsub[p];
+    double t[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = T[c * pitch + s];
+    if (hs.x) halo_face_monitor(H, H.hface[3 * u], 1, hs.x, t);
+    if (hs.y) halo_face_monitor(H, H.hface[3 * u + 1], 2, hs.y, t);
+    if (hs.z) halo_face_monitor(H, H.hface[3 * u + 2], 3, hs.z, t);
 }
 
 // The operator record of one un_ele as face_apply reads it: the element stencil, the face weights
@@ -241,6 +262,42 @@ __global__ __launch_bounds__(kBlock) void k_face(const double *X, double *OUT, c
     face_point<MODE>(xin, x, b, nb, u, stc, fface, fsx, hv, level1, rdt, omega, r);
 #pragma unroll
     for (int i = 0; i < 3; ++i) OUT[i * pitch + s] = r[i];
+}
+
+// get_residual's A tnew - RHS of the face operator reduced in registers (the convergence monitor,
+// pamg_params.monitor): k_face<3, UNI>'s loads and its face_point<3>, with the halo snapshot read from the
+// monitor's image, so every value is bitwise the one k_face<3, UNI> would store from t_overlap after the words
+// refresh; the three components go into the thread's record in component order, the workgroup's records through
+// the fixed tree (block_reduce), one record per workgroup into the slab (k_norm_combine finishes). 48 B per
+// sub-element in, nothing else stored; no floating-point atomics, no hand-off between workgroups
+template <bool UNI>
+__global__ __launch_bounds__(kBlock) void k_face_residual_reduce(
+    const double *__restrict__ X, const double *__restrict__ RHS, const double *__restrict__ stc,
+    const int4 *__restrict__ fnb, const double *__restrict__ fface, const int *__restrict__ fsx,
+    const double *__restrict__ img, int64_t pitch, int64_t N, int nsub_log2, int slots, int level1, double rdt,
+    NormRec *__restrict__ slab) {
+    __shared__ NormRec lds[kWaves];
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    NormRec rec = rec_identity();
+    if (s < N) {   // (UNI: N is a multiple of 64, a wave is inside or outside as a whole)
+        int64_t u = s >> nsub_log2;
+        if (UNI) u = __builtin_amdgcn_readfirstlane((int)u);
+        const int64_t base = u << nsub_log2;
+        const int4 nb = fnb[s & ((1ll << nsub_log2) - 1)];
+        double x[3], b[3], r[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            x[c] = X[c * pitch + s];
+            b[c] = RHS[c * pitch + s];
+        }
+        auto xin = [&](int c, int q) { return X[c * pitch + base + q]; };
+        auto hv = [&](int64_t uu, int mf, int sp, int k) { return img[uu * slots * 3 + (int64_t)(mf - 1) * slots + (sp - 1) * 3 + k]; };
+        face_point<3>(xin, x, b, nb, u, stc, fface, fsx, hv, level1, rdt, 0.0, r);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) rec_add(rec, r[i]);
+    }
+    rec = block_reduce(rec, lds);
+    if (threadIdx.x == 0) slab[blockIdx.x] = rec;
 }
 
 // One whole smoother sweep on a tile of TS sub-elements (whole un_eles; NT threads, TS / NT
@@ -2109,6 +2166,35 @@ hipError_t launch_face_words(hipStream_t s, const Level &L, int U, double *tov, 
     hipLaunchKernelGGL(k_face_words, dim3(grid_for(nwork)), dim3(kBlock), 0, s, L.T, L.pitch, H, P.d_bpos, P.nbpos,
                        nwork, log2i(L.nsub));
     return hipGetLastError();
+}
+
+hipError_t launch_face_monitor_words(hipStream_t s, const Level &L, int U, double *img, double *send3) {
+    const HaloPlan &P = L.halo;
+    const int64_t nwork = (int64_t)U * P.nbpos;
+    if (nwork == 0 || L.N == 0) return hipSuccess;
+    if (!img || (!send3 && !P.remote.empty())) return hipErrorInvalidValue;
+    HaloArgs H{P.d_hsub, P.d_hface, P.d_bcv, nullptr, img, nullptr, send3, 1 << L.isplit};
+    hipLaunchKernelGGL(k_face_monitor_words, dim3(grid_for(nwork)), dim3(kBlock), 0, s, L.T, L.pitch, H, P.d_bpos,
+                       P.nbpos, nwork, log2i(L.nsub));
+    return hipGetLastError();
+}
+
+size_t face_norm_slab_records(const Level &L) { return (size_t)grid_for(L.N); }
+
+hipError_t launch_face_residual_reduce(hipStream_t s, const Level &L, const double *img, bool level1, double rdt,
+                                       int slots, NormRec *slab, NormRec *out) {
+    if (L.N == 0) return hipSuccess;   // the caller holds the identities
+    if (!L.fnb || !L.fface || !L.fsx || !img) return hipErrorInvalidValue;
+    const unsigned g = grid_for(L.N);
+    const int lg = log2i(L.nsub), l1 = level1 ? 1 : 0;
+    if (L.nsub >= 64)
+        hipLaunchKernelGGL((k_face_residual_reduce<true>), dim3(g), dim3(kBlock), 0, s, L.T, L.RHS, L.stc, L.fnb, L.fface,
+                           L.fsx, img, L.pitch, L.N, lg, slots, l1, rdt, slab);
+    else
+        hipLaunchKernelGGL((k_face_residual_reduce<false>), dim3(g), dim3(kBlock), 0, s, L.T, L.RHS, L.stc, L.fnb,
+                           L.fface, L.fsx, img, L.pitch, L.N, lg, slots, l1, rdt, slab);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_norm_combine(s, slab, (int)g, out);
 }
 
 hipError_t launch_face_sweep(hipStream_t s, const Level &L, const double *tov, int mode, bool level1, double rdt,

@@ -281,6 +281,11 @@ struct pamg_handle {
     pamg_handle *tparent = nullptr;  // the replica's timing spans and fallback counts go to its parent's Timing
     // the reductions' read-back (pamg_field_norm, pamg_residual_norm): pinned, one record per rank (on first use)
     pamg::NormRec *norm_host = nullptr;
+    // the convergence monitor of the face operator (pamg_params.monitor = 1, op = 1; on the first check): an image
+    // of t_overlap's layout that holds the tnew-side halo words of the level being checked, and the send / receive
+    // words of their exchange between the ranks (3 per entry, sized for the largest level's plan). A check writes
+    // nothing else, so t_overlap, t_overlap_old and the exchange's own buffers stay as the cycles left them
+    double *mon_img = nullptr, *mon_send = nullptr, *mon_recv = nullptr;
 };
 
 // ---- setup (pamg_setup.cpp) ----
@@ -322,7 +327,8 @@ hipError_t launch_rhs(hipStream_t s, const Level &L, double rdt, int start_of_st
 hipError_t launch_source(hipStream_t s, const Level &L, const double *geo1, double k);
 hipError_t launch_halo_unpack(hipStream_t s, const Level &L, double *tov, double *tovo);
 // the tnew words of one cycle of the resident call's ring exchange (3 per entry, d_recv3) into t_overlap
-hipError_t launch_halo_unpack3(hipStream_t s, const Level &L, double *tov);
+// (recv3: the received words; null: the plan's d_recv3)
+hipError_t launch_halo_unpack3(hipStream_t s, const Level &L, double *tov, const double *recv3 = nullptr);
 hipError_t launch_copy(hipStream_t s, const double *src, double *dst, int64_t n);
 hipError_t launch_told_halo(hipStream_t s, const Level &L, int U);
 // from_told: read told from the TOLD planes and also write the compact told copy
@@ -479,6 +485,19 @@ size_t norm_slab_records(const Level &L);
 hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, NormRec *slab, NormRec *out);
 // A tnew - RHS of level L (k_residual's values, bitwise) reduced without being stored
 hipError_t launch_residual_reduce(hipStream_t s, const Level &L, double rdt, NormRec *slab, NormRec *out);
+// the one-workgroup combine launch of the passes above: the slab's n records into *out
+hipError_t launch_norm_combine(hipStream_t s, const NormRec *slab, int n, NormRec *out);
+// ---- the face operator's convergence monitor (pamg_face.hip) ----
+// the tnew-side halo words of level L from its tnew (launch_face_words' work list), into the monitor's image
+// `img` (t_overlap's layout) and, for neighbours on other ranks, 3 words per entry into `send3`; nothing of
+// t_overlap, t_overlap_old, the told halo or the exchange's send buffer is read or written
+hipError_t launch_face_monitor_words(hipStream_t s, const Level &L, int U, double *img, double *send3);
+// the face operator's A tnew - RHS of level L with the values across un_ele faces read from `img` (k_face<3>'s
+// values, bitwise), reduced without being stored: one record per workgroup into slab
+// (face_norm_slab_records(L) of them: one thread per sub-element), combined into *out
+size_t face_norm_slab_records(const Level &L);
+hipError_t launch_face_residual_reduce(hipStream_t s, const Level &L, const double *img, bool level1, double rdt,
+                                       int slots, NormRec *slab, NormRec *out);
 hipError_t launch_sweep_assembled(hipStream_t s, const Level &L, double *out, double rdt);
 hipError_t launch_sweep_stencil(hipStream_t s, const Level &L, double *out, double rdt);
 }  // namespace pamg

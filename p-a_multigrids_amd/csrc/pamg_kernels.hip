@@ -878,11 +878,12 @@ hipError_t launch_halo_unpack(hipStream_t s, const Level &L, double *tov, double
     return hipGetLastError();
 }
 
-hipError_t launch_halo_unpack3(hipStream_t s, const Level &L, double *tov) {
+hipError_t launch_halo_unpack3(hipStream_t s, const Level &L, double *tov, const double *recv3) {
     const HaloPlan &P = L.halo;
     const int n = (int)P.recv_dst.size();
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_halo_unpack3, dim3(grid_for(n)), dim3(kBlock), 0, s, P.d_recv3, P.d_recv_dst, n, tov);
+    hipLaunchKernelGGL(k_halo_unpack3, dim3(grid_for(n)), dim3(kBlock), 0, s, recv3 ? recv3 : P.d_recv3, P.d_recv_dst, n,
+                       tov);
     return hipGetLastError();
 }
 

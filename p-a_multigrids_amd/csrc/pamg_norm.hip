@@ -18,69 +18,15 @@
 
 #include "pamg_device.h"
 #include "pamg_internal.h"
+#include "pamg_norm_device.h"
 
 namespace pamg {
 namespace {
 
 using namespace detail;
 
-constexpr int kWaves = kBlock / 64;
 // the combine launch: one workgroup of 16 waves, 8 records in flight per thread
 constexpr int kCombineBlock = 1024, kCombineWaves = kCombineBlock / 64, kCombineBatch = 8;
-
-__device__ __forceinline__ NormRec rec_identity() {
-    NormRec r;
-    r.max = -__builtin_huge_val();
-    r.maxabs = 0.0;
-    r.sumsq = 0.0;
-    r.nonfinite = 0ull;
-    return r;
-}
-
-// one value into a record; the exponent test also catches what fmax would drop (NaN)
-__device__ __forceinline__ void rec_add(NormRec &r, double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    r.nonfinite |= (unsigned long long)((b & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
-    r.max = fmax(r.max, v);
-    r.maxabs = fmax(r.maxabs, __builtin_fabs(v));
-    r.sumsq = r.sumsq + v * v;
-}
-
-// a (the lower index) combined with b
-__device__ __forceinline__ NormRec rec_join(const NormRec &a, const NormRec &b) {
-    NormRec r;
-    r.max = fmax(a.max, b.max);
-    r.maxabs = fmax(a.maxabs, b.maxabs);
-    r.sumsq = a.sumsq + b.sumsq;
-    r.nonfinite = a.nonfinite | b.nonfinite;
-    return r;
-}
-
-__device__ __forceinline__ NormRec rec_shfl_down(const NormRec &a, int d) {
-    NormRec r;
-    r.max = __shfl_down(a.max, d, 64);
-    r.maxabs = __shfl_down(a.maxabs, d, 64);
-    r.sumsq = __shfl_down(a.sumsq, d, 64);
-    r.nonfinite = __shfl_down(a.nonfinite, d, 64);
-    return r;
-}
-
-// every thread of the workgroup (NW waves) calls it (threads past the tail with the identity); thread 0
-// returns the workgroup's record
-template <int NW = kWaves>
-__device__ __forceinline__ NormRec block_reduce(NormRec r, NormRec *lds) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) r = rec_join(r, rec_shfl_down(r, d));
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) lds[wave] = r;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        r = lds[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) r = rec_join(r, lds[w]);
-    }
-    return r;
-}
 
 // one state field: one thread per pair of sub-elements, 24 B per sub-element in, one record per workgroup out
 __global__ __launch_bounds__(kBlock) void k_field_reduce(const double *__restrict__ F, int64_t pitch, int64_t npairs,
@@ -165,6 +111,11 @@ inline unsigned grid_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBloc
 inline int log2i(int v) { int r = 0; while ((1 << r) < v) ++r; return r; }
 
 }  // namespace
+
+hipError_t launch_norm_combine(hipStream_t s, const NormRec *slab, int n, NormRec *out) {
+    hipLaunchKernelGGL(k_norm_combine, dim3(1), dim3(kCombineBlock), 0, s, slab, n, out);
+    return hipGetLastError();
+}
 
 size_t norm_slab_records(const Level &L) { return (size_t)grid_for(L.N / 2); }
 
