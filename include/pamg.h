@@ -47,6 +47,11 @@ extern "C" {
 #define PAMG_TNEW_NONLIN 4 /* tnew_nonlin (transport_tri_semi.F90:85), shape of its current level */
 #define PAMG_SOURCE 5      /* tracer(1)%source after get_RHS: level 1's cascaded source term s' (:452-464,
                               :593), formed once at upload; level 1 only, pamg_get_state only */
+#define PAMG_ERROR 6       /* tracer(1)%error = |tnew - analytical| (get_error, :531-540): level 1 only; zero until
+                              the first pamg_get_error (:239); read by pamg_get_state and pamg_field_norm, refused
+                              by pamg_set_state (PAMG_ERR_ARG). Its three planes are allocated zero-filled on the
+                              first of those calls that names it: a run that never does keeps its footprint. A
+                              failed allocation is PAMG_ERR_HIP and leaves the handle as it was */
 
 /* timed kernel classes (pamg_timing_*) */
 #define PAMG_K_SMOOTH_L1 0
@@ -72,7 +77,8 @@ extern "C" {
 #define PAMG_K_COARSE_GATHER 17  /* op = 1 on a partition: the ranks' coarsest-level blocks (RHS each cycle, tnew once
                                     per call) gathered into every rank's replica of that level (the agglomerated
                                     coarsest level: the single-domain chain runs on each rank) */
-#define PAMG_K_NORM 18           /* a reduction pass of pamg_field_norm / pamg_get_convergence (24 B per sub-element) or
+#define PAMG_K_NORM 18           /* a reduction pass of pamg_field_norm / pamg_get_convergence / pamg_error_norm (24 B per
+                                    sub-element), pamg_get_error's store pass (24 B in, 24 B out) or
                                     pamg_residual_norm / pamg_solve (tnew and RHS in, no field out: 48 B per
                                     sub-element + the operator records), with its one-workgroup combine launch;
                                     op = 1 (monitor = 1): the monitor words launch, their exchange between the
@@ -241,6 +247,13 @@ int pamg_synchronize(pamg_handle *h);
 #define PAMG_NORM_REF    0  /* the reference's get_convergence: max(0, max_i r_i), signed; its loop starts from 0.0 (:879-887) */
 #define PAMG_NORM_MAXABS 1  /* max_i |r_i| */
 #define PAMG_NORM_L2     2  /* sqrt(sum_i r_i^2) */
+/* pamg_field_norm and pamg_error_norm only (the residual forms -- pamg_residual_norm, pamg_get_convergence,
+ * pamg_solve -- accept kinds 0, 1 and 2): */
+#define PAMG_NORM_L1      3 /* sum_i |v_i|: the pointwise L1 of the reference's post-processing */
+#define PAMG_NORM_L2_MASS 4 /* sqrt(sum_s v_s^T M_s v_s), M_s the level's own mass matrix of the sub-element
+                               (the operator record's M_12 [[2,1,1],[1,2,1],[1,1,2]]): the L2(Omega) norm of the
+                               P1 field, comparable between two n_split where the discrete L2 grows with the node
+                               count */
 
 /* read-only reduction of a state field (selectors of pamg_get_state); the state is untouched.
  * PAMG_ERR_ARG on the agglomerated coarsest level of an op = 1 partition (replicated, not partitioned) */
@@ -248,6 +261,18 @@ int pamg_field_norm(pamg_handle *h, int level, int what, int kind, double *value
 /* `call get_convergence` (:876-889): pamg_get_residual(level), then PAMG_NORM_REF of tracer(level)%residuale.
  * The state after the call is that after pamg_get_residual(level). */
 int pamg_get_convergence(pamg_handle *h, int level, double *convergence);
+/* `call get_error` (:303, body :531-540): tracer(1)%error := |tracer(1)%tnew - analytical| on level 1, with
+ * analytical = sin(x + y) (boundary(), splitting.F90:1401-1405) at the get_splitting nodes (:277-279) recomputed in
+ * the kernel from the un_ele geometry -- the reference's `analytical` array is not kept. Every other field, the halo
+ * words and the host-side flags stay as they were. Accepted for every op, solver, cycle, arith and coarse_solver
+ * (the error depends on no operator). Ordered on the handle's stream; read the field with pamg_get_state(1,
+ * PAMG_ERROR) or reduce it with pamg_field_norm(1, PAMG_ERROR, kind). */
+int pamg_get_error(pamg_handle *h);
+/* the same values reduced in registers: no store, no allocation of the error field, nothing in the handle changes,
+ * so the cycles after it are bitwise those without it. Every reduced value is bitwise the one pamg_get_error would
+ * store and enters the reduction in pamg_field_norm's order: for every kind (0 .. 4) the result equals
+ * pamg_get_error followed by pamg_field_norm(1, PAMG_ERROR, kind) on the float. Partitions as the other norms. */
+int pamg_error_norm(pamg_handle *h, int kind, double *value);
 /* the same residual A tnew - RHS reduced without being stored: no field, halo word or host-side flag
  * (rhsn_valid, overlap_static_l1, tnn_level, ...) changes, so the cycles after it are bitwise those without it
  * (pamg_get_residual between two cycles of cycle = 0 is not: the next restrictor reads the residual the

@@ -186,6 +186,7 @@ double *field_ptr(pamg_handle *h, int l, int what) {
         case PAMG_RESIDUAL: return L.RES;
         case PAMG_TNEW_NONLIN: return L.TNN;
         case PAMG_SOURCE: return L.SRC;   // level 1 only (null elsewhere)
+        case PAMG_ERROR: return L.ERR;    // level 1 only, and null until error_setup
     }
     return nullptr;
 }
@@ -2267,11 +2268,17 @@ double norm_value(const NormRec &r, int kind) {
     switch (kind) {
         case PAMG_NORM_REF: return r.max > 0.0 ? r.max : 0.0;   // get_convergence's loop starts from 0.0 (:879)
         case PAMG_NORM_MAXABS: return r.maxabs;
-        default: return std::sqrt(r.sumsq);
+        case PAMG_NORM_L1: return r.sumsq;   // the pass accumulated |v| into the sum word (norm_mode)
+        default: return std::sqrt(r.sumsq);  // L2: the squares; L2_MASS: v^T M v per sub-element
     }
 }
 
+// the kinds of the residual forms (pamg_residual_norm, pamg_get_convergence, pamg_solve)
 bool norm_kind_ok(int kind) { return kind == PAMG_NORM_REF || kind == PAMG_NORM_MAXABS || kind == PAMG_NORM_L2; }
+// ... and of pamg_field_norm / pamg_error_norm
+bool field_kind_ok(int kind) { return norm_kind_ok(kind) || kind == PAMG_NORM_L1 || kind == PAMG_NORM_L2_MASS; }
+// what a reduction pass accumulates into the record's sum word for `kind` (pamg_norm_device.h kAcc*)
+int norm_mode(int kind) { return kind == PAMG_NORM_L1 ? 1 : kind == PAMG_NORM_L2_MASS ? 2 : 0; }
 
 // the local group's gather: this rank's record into its slot, every rank's slot of the same reduction out
 int norm_meet_local(pamg_handle *h, const NormRec &mine, NormRec *all) {
@@ -2344,10 +2351,15 @@ int monitor_exchange(pamg_handle *h, int l) {
     return PAMG_OK;
 }
 
-// residual_form with op = 1: the face form -- the monitor words of the level, their exchange, then the
+// form: kFormField a state field, kFormResidual A tnew - RHS in registers, kFormError level 1's
+// |tnew - sin(x + y)| in registers (get_error's values, not stored); mode: norm_mode(kind).
+// kFormResidual with op = 1: the face form -- the monitor words of the level, their exchange, then the
 // reduction of the face operator's residual from the monitor's image
-int norm_reduce(pamg_handle *h, int l, const double *field, bool residual_form, NormRec *res) {
+enum { kFormField = 0, kFormResidual = 1, kFormError = 2 };
+
+int norm_reduce(pamg_handle *h, int l, const double *field, int form, int mode, NormRec *res) {
     Level &L = h->lv[l];
+    const bool residual_form = form == kFormResidual;
     const bool face = residual_form && h->p.op == 1;
     if (h->comm && !h->comm->nccl && !h->comm->local) {
         h->err = "norm: the communicator was aborted";
@@ -2377,7 +2389,8 @@ int norm_reduce(pamg_handle *h, int l, const double *field, bool residual_form, 
     } else if (!empty) {
         Span sp(h, PAMG_K_NORM, residual_form ? 48.0 * (double)L.N + 168.0 * h->U : 24.0 * (double)L.N);
         if (residual_form) HIPCHK(h, launch_residual_reduce(h->stream, L, 1 / h->p.dt, d_slab, d_rec));
-        else HIPCHK(h, launch_field_reduce(h->stream, L, field, d_slab, d_rec));
+        else if (form == kFormError) HIPCHK(h, launch_error_reduce(h->stream, L, h->geo1, mode, d_slab, d_rec));
+        else HIPCHK(h, launch_field_reduce(h->stream, L, field, mode, d_slab, d_rec));
     }
     if (rccl) {
         if (empty) {
@@ -2442,14 +2455,33 @@ int residual_norm_ok(pamg_handle *h) {
 
 int residual_norm(pamg_handle *h, int level, int kind, double *value) {
     NormRec r;
-    CHK(norm_reduce(h, level, nullptr, true, &r));
+    CHK(norm_reduce(h, level, nullptr, kFormResidual, 0, &r));
     *value = norm_value(r, kind);
+    return PAMG_OK;
+}
+
+// tracer(1)%error: its three planes on the first call that names the field, zero-filled (the reference's
+// allocation, :239) -- as monitor_setup does for the monitor's image, so a run that never asks for the field
+// keeps its footprint. A failed allocation leaves the handle as it was
+int error_setup(pamg_handle *h) {
+    Level &L = h->lv[1];
+    if (L.ERR) return PAMG_OK;
+    double *e = nullptr;
+    CHK(dev_alloc(h, &e, 3 * (size_t)L.pitch));
+    if (hipMemsetAsync(e, 0, 3 * (size_t)L.pitch * sizeof(double), h->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        dev_free(e);
+        h->err = "error field: hipMemsetAsync failed";
+        return PAMG_ERR_HIP;
+    }
+    L.ERR = e;
     return PAMG_OK;
 }
 
 void free_levels(pamg_handle *h) {
     for (int l = 1; l <= kMaxLevels; ++l) {
         Level &L = h->lv[l];
+        dev_free(L.ERR);
         dev_free(L.T); dev_free(L.stc); dev_free(L.Ainv); dev_free(L.subinfo); dev_free(L.d_pos); dev_free(L.blocks);
         dev_free(L.fnb); dev_free(L.fface); dev_free(L.fsx); dev_free(L.cpos); dev_free(L.gtab); dev_free(L.cnb); dev_free(L.gpat);
         dev_free(L.chain_nb_off); dev_free(L.chain_nb_list); dev_free(L.chain_flags);
@@ -2930,7 +2962,8 @@ int pamg_set_state(pamg_handle *h, int level, int what, const double *host) {
     if (what == PAMG_TNEW_NONLIN) { CHK(check_level(h, level)); h->tnn_level = level; }
     CHK(check_level(h, level));
     Level &L = h->lv[level];
-    double *dst = what == PAMG_SOURCE ? nullptr : field_ptr(h, level, what);   // the source is read-only
+    // the source is read-only, and so is the error: only pamg_get_error writes it
+    double *dst = what == PAMG_SOURCE || what == PAMG_ERROR ? nullptr : field_ptr(h, level, what);
     if (!dst) return PAMG_ERR_ARG;
     CHK(ensure_scratch(h, 3 * (size_t)L.N * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->scratch, host, 3 * (size_t)L.N * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -2947,6 +2980,7 @@ int pamg_get_state(pamg_handle *h, int level, int what, double *host) {
     if (what == PAMG_TNEW_NONLIN) level = h->tnn_level;
     CHK(check_level(h, level));
     Level &L = h->lv[level];
+    if (what == PAMG_ERROR && level == 1) CHK(error_setup(h));
     double *src = field_ptr(h, level, what);
     if (!src) return PAMG_ERR_ARG;
     CHK(ensure_scratch(h, 3 * (size_t)L.N * sizeof(double)));
@@ -3083,15 +3117,40 @@ int pamg_vcycle(pamg_handle *h, int n) {
 
 int pamg_field_norm(pamg_handle *h, int level, int what, int kind, double *value) {
     if (!h || !value) return PAMG_ERR_ARG;
-    if (!norm_kind_ok(kind)) { h->err = "norm: unknown kind"; return PAMG_ERR_ARG; }
+    if (!field_kind_ok(kind)) { h->err = "norm: unknown kind"; return PAMG_ERR_ARG; }
     CHK(settle(h));
     if (what == PAMG_TNEW_NONLIN) level = h->tnn_level;   // as pamg_get_state
     CHK(check_level(h, level));
     CHK(norm_level_ok(h, level));
+    if (what == PAMG_ERROR && level == 1) CHK(error_setup(h));
     const double *src = field_ptr(h, level, what);
     if (!src) { h->err = "norm: no such field on this level"; return PAMG_ERR_ARG; }
     NormRec r;
-    CHK(norm_reduce(h, level, src, false, &r));
+    CHK(norm_reduce(h, level, src, kFormField, norm_mode(kind), &r));
+    *value = norm_value(r, kind);
+    return PAMG_OK;
+}
+
+// `call get_error` (:303, body :531-540): tracer(1)%error := |tnew - analytical| on level 1; nothing else is written
+int pamg_get_error(pamg_handle *h) {
+    if (!h) return PAMG_ERR_ARG;
+    CHK(settle(h));
+    CHK(check_level(h, 1));
+    CHK(error_setup(h));
+    Level &L = h->lv[1];
+    if (L.N == 0) return PAMG_OK;   // a rank that owns nothing
+    Span sp(h, PAMG_K_NORM, 48.0 * (double)L.N);
+    HIPCHK(h, launch_error(h->stream, L, h->geo1, L.ERR));
+    return PAMG_OK;
+}
+
+int pamg_error_norm(pamg_handle *h, int kind, double *value) {
+    if (!h || !value) return PAMG_ERR_ARG;
+    if (!field_kind_ok(kind)) { h->err = "norm: unknown kind"; return PAMG_ERR_ARG; }
+    CHK(settle(h));
+    CHK(check_level(h, 1));
+    NormRec r;
+    CHK(norm_reduce(h, 1, nullptr, kFormError, norm_mode(kind), &r));
     *value = norm_value(r, kind);
     return PAMG_OK;
 }
@@ -3103,7 +3162,7 @@ int pamg_get_convergence(pamg_handle *h, int level, double *convergence) {
     CHK(norm_level_ok(h, level));
     CHK(residual(h, level));   // `call get_residual(ilevel)` (:877)
     NormRec r;
-    CHK(norm_reduce(h, level, h->lv[level].RES, false, &r));
+    CHK(norm_reduce(h, level, h->lv[level].RES, kFormField, 0, &r));
     *convergence = norm_value(r, PAMG_NORM_REF);
     return PAMG_OK;
 }

@@ -355,6 +355,31 @@ __device__ __forceinline__ void source_one(const double *__restrict__ g, const d
     for (int i = 0; i < 3; ++i) src[i] = M[3 * i] * src[0] + M[3 * i + 1] * src[1] + M[3 * i + 2] * src[2];
 }
 
+// get_error's |tnew - analytical| of one level-1 sub-element (transport_tri_semi.F90:531-540): analytical is
+// boundary(x, y) = sin(x + y) (splitting.F90:1401-1405) at the get_splitting nodes (:277-279), recomputed from
+// the un_ele's geometry record g and the sub-element's (irow, ipos) -- source_one's coordinate expressions, for
+// up (odd ipos) and down sub-elements, which are the host's get_splitting (pamg_setup.cpp) operation for
+// operation. The one definition k_error and k_error_reduce share, so that both form the same bits.
+__device__ __forceinline__ void error_one(const double *__restrict__ g, int2 ri, const double t[3], double e[3]) {
+    const int irow = ri.x, ipos = ri.y;
+    double xl[3][2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        const double x3 = g[d], v1 = g[2 + d], v2 = g[4 + d];
+        if (ipos % 2 != 0) {
+            xl[2][d] = x3 + (double)(irow - 1) * v2 + (double)(ipos / 2) * v1;
+            xl[1][d] = x3 + (double)irow * v2 + (double)(ipos / 2) * v1;
+            xl[0][d] = x3 + (double)(irow - 1) * v2 + v1 * (double)(ipos / 2 + 1);
+        } else {
+            xl[0][d] = x3 + (double)irow * v2 + v1 * (double)(ipos / 2 - 1);
+            xl[1][d] = x3 + (double)(irow - 1) * v2 + v1 * (double)(ipos / 2);
+            xl[2][d] = x3 + (double)irow * v2 + v1 * (double)(ipos / 2);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) e[i] = __builtin_fabs(t[i] - sin(xl[i][0] + xl[i][1]));
+}
+
 // Level-1 RHS of one sub-element from its told t and its s' (get_RHS :452-464):
 // RHS_i = rdt (M t)_i + s'_i, the reference's operation order; (M t)_i is evaluated from
 // c = M_12 as in apply_A, bit for bit the reference's (M_i1 t_1 + M_i2 t_2) + M_i3 t_3.

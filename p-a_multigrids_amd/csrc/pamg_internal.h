@@ -94,6 +94,10 @@ struct Level {
     // s_j = -2k sin(x_j + y_j) at the sub-element nodes -- geometry only, formed once at upload
     // (k_source) and added to rdt M told by every RHS evaluation
     double *SRC = nullptr;
+    // level 1 only: tracer(1)%error = |tnew - sin(x + y)| (get_error, transport_tri_semi.F90:531-540), three planes
+    // of its own, allocated zero-filled on the first pamg_get_error / pamg_get_state / pamg_field_norm of
+    // PAMG_ERROR (pamg_api.cpp error_setup): a run that never asks for it keeps its footprint
+    double *ERR = nullptr;
     double *stc = nullptr;            // U_local * kStcStride
     int2 *subinfo = nullptr;          // nsub: (irow, ipos) of get_str_info, by storage position
     // Storage order of the sub-elements of an un_ele: hierarchical, not the
@@ -482,7 +486,15 @@ hipError_t launch_face_chain(hipStream_t s, const Level &L, int U, int cus, doub
 // one pass over level L: a partial record per workgroup into slab (norm_slab_records(L) of them), combined
 // by a second, one-workgroup launch into *out; L.N == 0 launches nothing (the caller holds the identities)
 size_t norm_slab_records(const Level &L);
-hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, NormRec *slab, NormRec *out);
+// mode: what the record's sum word accumulates (0 squares, 1 magnitudes, 2 the mass-weighted term per sub-element;
+// pamg_norm_device.h kAccSq / kAccAbs / kAccMass)
+hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, int mode, NormRec *slab,
+                               NormRec *out);
+// get_error (:531-540) on level 1: err (3 planes of L.pitch) := |tnew - sin(x + y)| at the get_splitting nodes
+hipError_t launch_error(hipStream_t s, const Level &L, const double *geo1, double *err);
+// the same values reduced without being stored (bitwise those launch_error stores, in launch_field_reduce's order)
+hipError_t launch_error_reduce(hipStream_t s, const Level &L, const double *geo1, int mode, NormRec *slab,
+                               NormRec *out);
 // A tnew - RHS of level L (k_residual's values, bitwise) reduced without being stored
 hipError_t launch_residual_reduce(hipStream_t s, const Level &L, double rdt, NormRec *slab, NormRec *out);
 // the one-workgroup combine launch of the passes above: the slab's n records into *out

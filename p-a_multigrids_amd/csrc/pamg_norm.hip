@@ -1,5 +1,6 @@
 // Device reductions of libpamg (gfx950): one pass over a level produces the record
-// {max, maxabs, sumsq, nonfinite} of a state field (k_field_reduce) or of the residual
+// {max, maxabs, sumsq, nonfinite} of a state field (k_field_reduce), of level 1's error |tnew - sin(x + y)|
+// computed on the fly (k_error_reduce; k_error stores it, get_error :531-540) or of the residual
 // A tnew - RHS computed on the fly (k_residual_reduce), which stores no field: the convergence
 // monitor of pamg_residual_norm / pamg_solve must leave the state untouched (the reference
 // cycle's restrictor reads the residual the previous cycle left, transport_tri_semi.F90:336-338,
@@ -28,8 +29,12 @@ using namespace detail;
 // the combine launch: one workgroup of 16 waves, 8 records in flight per thread
 constexpr int kCombineBlock = 1024, kCombineWaves = kCombineBlock / 64, kCombineBatch = 8;
 
-// one state field: one thread per pair of sub-elements, 24 B per sub-element in, one record per workgroup out
-__global__ __launch_bounds__(kBlock) void k_field_reduce(const double *__restrict__ F, int64_t pitch, int64_t npairs,
+// one state field: one thread per pair of sub-elements, 24 B per sub-element in, one record per workgroup out.
+// MODE (pamg_norm_device.h): what goes into the record's sum word; kAccMass reads M_12 of the pair's un_ele from
+// the level's operator record (a pair never straddles two un_eles: nsub is a power of 4)
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_field_reduce(const double *__restrict__ F, const double *__restrict__ stc,
+                                                         int64_t pitch, int64_t npairs, int nsub_log2,
                                                          NormRec *__restrict__ slab) {
     __shared__ NormRec lds[kWaves];
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -39,10 +44,60 @@ __global__ __launch_bounds__(kBlock) void k_field_reduce(const double *__restric
         double2 v[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = ld2(F + c * pitch + s);
+        const double m12 = MODE == kAccMass ? stc[(s >> nsub_log2) * kStcStride + kStcM + 1] : 0.0;
+        const double v0[3] = {v[0].x, v[1].x, v[2].x}, v1[3] = {v[0].y, v[1].y, v[2].y};
+        rec_add_sub<MODE>(r, v0, m12);
+        rec_add_sub<MODE>(r, v1, m12);
+    }
+    r = block_reduce(r, lds);
+    if (threadIdx.x == 0) slab[blockIdx.x] = r;
+}
+
+// get_error (transport_tri_semi.F90:531-540): tracer(1)%error = |tnew - sin(x + y)| at the get_splitting nodes,
+// the analytical value recomputed from the geometry records (error_one) and never stored; 24 B per sub-element
+// in, 24 B out
+__global__ __launch_bounds__(kBlock) void k_error(const double *__restrict__ T, double *__restrict__ E,
+                                                  const double *__restrict__ geo, const int2 *__restrict__ subinfo,
+                                                  int64_t pitch, int64_t npairs, int nsub_log2) {
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= npairs) return;
+    const int64_t s = 2 * p, u = s >> nsub_log2;
+    const int sub = (int)(s & ((1ll << nsub_log2) - 1));
+    double2 tv[3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) rec_add(r, v[c].x);
+    for (int c = 0; c < 3; ++c) tv[c] = ld2(T + c * pitch + s);
+    const double t0[3] = {tv[0].x, tv[1].x, tv[2].x}, t1[3] = {tv[0].y, tv[1].y, tv[2].y};
+    double e0[3], e1[3];
+    error_one(geo + u * kGeoStride, subinfo[sub], t0, e0);
+    error_one(geo + u * kGeoStride, subinfo[sub + 1], t1, e1);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) rec_add(r, v[c].y);
+    for (int c = 0; c < 3; ++c) st2(E + c * pitch + s, make_double2(e0[c], e1[c]));
+}
+
+// the same values reduced in registers: k_error's loads and its error_one, fed to the workgroup's tree in
+// k_field_reduce's order, so every value is bitwise the one k_error would store and every kind equals
+// k_error + k_field_reduce on the float; 24 B per sub-element in, no field out
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_error_reduce(const double *__restrict__ T, const double *__restrict__ geo,
+                                                         const int2 *__restrict__ subinfo,
+                                                         const double *__restrict__ stc, int64_t pitch, int64_t npairs,
+                                                         int nsub_log2, NormRec *__restrict__ slab) {
+    __shared__ NormRec lds[kWaves];
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    NormRec r = rec_identity();
+    if (p < npairs) {
+        const int64_t s = 2 * p, u = s >> nsub_log2;
+        const int sub = (int)(s & ((1ll << nsub_log2) - 1));
+        double2 tv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tv[c] = ld2(T + c * pitch + s);
+        const double m12 = MODE == kAccMass ? stc[u * kStcStride + kStcM + 1] : 0.0;
+        const double t0[3] = {tv[0].x, tv[1].x, tv[2].x}, t1[3] = {tv[0].y, tv[1].y, tv[2].y};
+        double e0[3], e1[3];
+        error_one(geo + u * kGeoStride, subinfo[sub], t0, e0);
+        error_one(geo + u * kGeoStride, subinfo[sub + 1], t1, e1);
+        rec_add_sub<MODE>(r, e0, m12);
+        rec_add_sub<MODE>(r, e1, m12);
     }
     r = block_reduce(r, lds);
     if (threadIdx.x == 0) slab[blockIdx.x] = r;
@@ -119,11 +174,47 @@ hipError_t launch_norm_combine(hipStream_t s, const NormRec *slab, int n, NormRe
 
 size_t norm_slab_records(const Level &L) { return (size_t)grid_for(L.N / 2); }
 
-hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, NormRec *slab, NormRec *out) {
+hipError_t launch_field_reduce(hipStream_t s, const Level &L, const double *field, int mode, NormRec *slab,
+                               NormRec *out) {
     const int64_t npairs = L.N / 2;
     if (npairs == 0) return hipSuccess;   // the caller supplies the identities
     const unsigned g = grid_for(npairs);
-    hipLaunchKernelGGL(k_field_reduce, dim3(g), dim3(kBlock), 0, s, field, L.pitch, npairs, slab);
+    const int lg = log2i(L.nsub);
+    if (mode == kAccMass)
+        hipLaunchKernelGGL((k_field_reduce<kAccMass>), dim3(g), dim3(kBlock), 0, s, field, L.stc, L.pitch, npairs, lg, slab);
+    else if (mode == kAccAbs)
+        hipLaunchKernelGGL((k_field_reduce<kAccAbs>), dim3(g), dim3(kBlock), 0, s, field, L.stc, L.pitch, npairs, lg, slab);
+    else
+        hipLaunchKernelGGL((k_field_reduce<kAccSq>), dim3(g), dim3(kBlock), 0, s, field, L.stc, L.pitch, npairs, lg, slab);
+    hipLaunchKernelGGL(k_norm_combine, dim3(1), dim3(kCombineBlock), 0, s, slab, (int)g, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_error(hipStream_t s, const Level &L, const double *geo1, double *err) {
+    const int64_t npairs = L.N / 2;
+    if (npairs == 0) return hipSuccess;
+    if (!err || !geo1 || !L.subinfo) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_error, dim3(grid_for(npairs)), dim3(kBlock), 0, s, L.T, err, geo1, L.subinfo, L.pitch, npairs,
+                       log2i(L.nsub));
+    return hipGetLastError();
+}
+
+hipError_t launch_error_reduce(hipStream_t s, const Level &L, const double *geo1, int mode, NormRec *slab,
+                               NormRec *out) {
+    const int64_t npairs = L.N / 2;
+    if (npairs == 0) return hipSuccess;
+    if (!geo1 || !L.subinfo) return hipErrorInvalidValue;
+    const unsigned g = grid_for(npairs);
+    const int lg = log2i(L.nsub);
+    if (mode == kAccMass)
+        hipLaunchKernelGGL((k_error_reduce<kAccMass>), dim3(g), dim3(kBlock), 0, s, L.T, geo1, L.subinfo, L.stc, L.pitch,
+                           npairs, lg, slab);
+    else if (mode == kAccAbs)
+        hipLaunchKernelGGL((k_error_reduce<kAccAbs>), dim3(g), dim3(kBlock), 0, s, L.T, geo1, L.subinfo, L.stc, L.pitch,
+                           npairs, lg, slab);
+    else
+        hipLaunchKernelGGL((k_error_reduce<kAccSq>), dim3(g), dim3(kBlock), 0, s, L.T, geo1, L.subinfo, L.stc, L.pitch,
+                           npairs, lg, slab);
     hipLaunchKernelGGL(k_norm_combine, dim3(1), dim3(kCombineBlock), 0, s, slab, (int)g, out);
     return hipGetLastError();
 }

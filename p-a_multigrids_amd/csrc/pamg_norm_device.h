@@ -32,6 +32,35 @@ __device__ __forceinline__ void rec_add(NormRec &r, double v) {
     r.sumsq = r.sumsq + v * v;
 }
 
+// What a reduction kernel accumulates into the record's sum word (the record itself is shared with the face
+// residual reduction and the ranks' 4-word gather, so it keeps its layout): kAccSq the squares (PAMG_NORM_REF,
+// MAXABS, L2 -- rec_add, value by value), kAccAbs the magnitudes (PAMG_NORM_L1), kAccMass one term per
+// sub-element, v^T M v with M = M_12 [[2,1,1],[1,2,1],[1,1,2]] = M_12 ((v0 + v1 + v2)^2 + v0^2 + v1^2 + v2^2)
+// (PAMG_NORM_L2_MASS). The maxima and the non-finite word are the same in all three.
+constexpr int kAccSq = 0, kAccAbs = 1, kAccMass = 2;
+
+// the three values of one sub-element into a record, component order (m12: kAccMass only)
+template <int MODE>
+__device__ __forceinline__ void rec_add_sub(NormRec &r, const double v[3], double m12) {
+    if constexpr (MODE == kAccSq) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rec_add(r, v[c]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const unsigned long long b = (unsigned long long)__double_as_longlong(v[c]);
+            r.nonfinite |= (unsigned long long)((b & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
+            r.max = fmax(r.max, v[c]);
+            r.maxabs = fmax(r.maxabs, __builtin_fabs(v[c]));
+            if constexpr (MODE == kAccAbs) r.sumsq = r.sumsq + __builtin_fabs(v[c]);
+        }
+        if constexpr (MODE == kAccMass) {
+            const double sv = v[0] + v[1] + v[2];
+            r.sumsq = r.sumsq + m12 * (sv * sv + v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        }
+    }
+}
+
 // a (the lower index) combined with b
 __device__ __forceinline__ NormRec rec_join(const NormRec &a, const NormRec &b) {
     NormRec r;

@@ -15,6 +15,10 @@ module pamg
   integer(c_int), parameter, public :: PAMG_TNEW_NONLIN = 4, PAMG_SOURCE = 5
   ! kinds of the norms and pamg_solve's status (include/pamg.h)
   integer(c_int), parameter, public :: PAMG_NORM_REF = 0, PAMG_NORM_MAXABS = 1, PAMG_NORM_L2 = 2
+  ! pamg_field_norm / pamg_error_norm only
+  integer(c_int), parameter, public :: PAMG_NORM_L1 = 3, PAMG_NORM_L2_MASS = 4
+  ! tracer(1)%error (pamg_get_state / pamg_field_norm selector)
+  integer(c_int), parameter, public :: PAMG_ERROR = 6
   integer(c_int), parameter, public :: PAMG_SOLVE_CONVERGED = 0, PAMG_SOLVE_MAXCYCLES = 1, PAMG_SOLVE_NONFINITE = 2
 
   type, bind(C), public :: pamg_params
@@ -37,6 +41,7 @@ module pamg
   public :: pamg_destroy, pamg_last_error, pamg_check, c_path, pamg_block_inverse, pamg_direct_solve
   public :: pamg_write_vtu, pamg_csr_create, pamg_csr_mul_array, pamg_csr_free, pamg_tnn_level
   public :: pamg_field_norm, pamg_get_convergence, pamg_residual_norm, pamg_solve
+  public :: pamg_get_error, pamg_error_norm
 
   interface
     subroutine pamg_default_params(p) bind(C, name='pamg_default_params')
@@ -148,6 +153,16 @@ module pamg
       import :: c_int, c_ptr, c_double
       type(c_ptr), value :: h
       integer(c_int), value :: level, kind
+      real(c_double), intent(out) :: value
+    end function
+    integer(c_int) function pamg_get_error(h) bind(C, name='pamg_get_error')
+      import :: c_int, c_ptr
+      type(c_ptr), value :: h
+    end function
+    integer(c_int) function pamg_error_norm(h, kind, value) bind(C, name='pamg_error_norm')
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: h
+      integer(c_int), value :: kind
       real(c_double), intent(out) :: value
     end function
     integer(c_int) function pamg_solve(h, kind, tol, max_cycles, check_every, cycles, value, status, history, &

@@ -20,6 +20,9 @@
 ! V-cycles in calls of check_every (default 1) cycles until max |A tnew - RHS| of level 1 is <= solve_tol
 ! or n_multigrid cycles have run -- and prints `convergence` and the cycle count. The default
 ! solve_tol = -1.0 leaves the run as it was.
+! report_error=1 prints, after the time loop, one line `error maxabs l2 l2_mass` (ES25.17): the norms of
+! |tnew - sin(x + y)| on level 1 that the reference's get_error (:303, :531-540) forms, reduced on the device by
+! pamg_error_norm (nothing is stored). The default 0 leaves the output as it was.
 program pamg_transport
   use iso_c_binding
   use pamg
@@ -36,8 +39,10 @@ program pamg_transport
   integer :: check_every = 1
   integer(c_int) :: solve_cycles, solve_status, solve_checks
   real(c_double) :: solve_history(1)
+  integer :: report_error = 0
+  real(c_double) :: err_maxabs, err_l2, err_l2_mass
   namelist /transport/ mesh_file, n_split, multi_levels, n_smooth, solver, ntime, n_multigrid, device, dump, &
-       call_sites, facade_sweeps, vtk_interval, cycle, solve_tol, check_every
+       call_sites, facade_sweeps, vtk_interval, cycle, solve_tol, check_every, report_error
 
   character(len=512) :: cfg
   type(c_ptr) :: m = c_null_ptr, h = c_null_ptr
@@ -143,6 +148,13 @@ program pamg_transport
   print *, '----------------------------------------------------------'
   print *, '|        cpu_time for time_loop = ', real(c1 - c0, 8) / real(crate, 8), '|'
   print *, '----------------------------------------------------------'
+
+  if (report_error == 1) then                               ! get_error (:303), reduced instead of stored
+    call pamg_check(pamg_error_norm(h, PAMG_NORM_MAXABS, err_maxabs), h, 'pamg_error_norm')
+    call pamg_check(pamg_error_norm(h, PAMG_NORM_L2, err_l2), h, 'pamg_error_norm')
+    call pamg_check(pamg_error_norm(h, PAMG_NORM_L2_MASS, err_l2_mass), h, 'pamg_error_norm')
+    write(*, '(a,3(1x,es25.17))') ' error', err_maxabs, err_l2, err_l2_mass
+  end if
 
   if (len_trim(dump) > 0) call write_dump(h, trim(dump), int(U), n_split, multi_levels)
   call pamg_check(pamg_destroy(h), c_null_ptr, 'pamg_destroy')

@@ -17,7 +17,7 @@ PAMG_OK = 0
 ERRORS = {-1: "PAMG_ERR_ARG", -2: "PAMG_ERR_HIP", -3: "PAMG_ERR_IO", -4: "PAMG_ERR_STATE",
           -5: "PAMG_ERR_COMM", -6: "PAMG_ERR_NODEV"}
 
-TNEW, TOLD, RHS, RESIDUAL, TNEW_NONLIN, SOURCE = 0, 1, 2, 3, 4, 5
+TNEW, TOLD, RHS, RESIDUAL, TNEW_NONLIN, SOURCE, ERROR = 0, 1, 2, 3, 4, 5, 6
 (K_SMOOTH_L1, K_SMOOTH, K_RESIDUAL, K_RESTRICT, K_PROLONG, K_RHS, K_HALO, K_SWEEP_BENCH, K_VCYCLE,
  K_VCYCLE_COARSE) = range(10)
 K_NAMES = ["smooth_L1", "smooth", "residual", "restrict", "prolong", "rhs", "halo", "sweep_bench", "vcycle",
@@ -26,6 +26,8 @@ K_NAMES = ["smooth_L1", "smooth", "residual", "restrict", "prolong", "rhs", "hal
 K_NORM = K_NAMES.index("norm")
 # kinds of pamg_field_norm / pamg_residual_norm / pamg_solve (PAMG_NORM_REF, PAMG_NORM_MAXABS, PAMG_NORM_L2)
 NORM_REF, NORM_MAXABS, NORM_L2 = 0, 1, 2
+# pamg_field_norm / pamg_error_norm only (PAMG_NORM_L1, PAMG_NORM_L2_MASS)
+NORM_L1, NORM_L2_MASS = 3, 4
 # pamg_solve's status (PAMG_SOLVE_CONVERGED, PAMG_SOLVE_MAXCYCLES, PAMG_SOLVE_NONFINITE)
 SOLVE_CONVERGED, SOLVE_MAXCYCLES, SOLVE_NONFINITE = 0, 1, 2
 
@@ -89,6 +91,8 @@ def lib():
         "pamg_field_norm": (I, [P, I, I, I, C.POINTER(D)]),
         "pamg_get_convergence": (I, [P, I, C.POINTER(D)]),
         "pamg_residual_norm": (I, [P, I, I, C.POINTER(D)]),
+        "pamg_get_error": (I, [P]),
+        "pamg_error_norm": (I, [P, I, C.POINTER(D)]),
         "pamg_solve": (I, [P, I, D, I, I, C.POINTER(I), C.POINTER(D), C.POINTER(I), C.c_void_p, I, C.POINTER(I)]),
         "pamg_timing_enable": (I, [P, C.c_uint]),
         "pamg_timing_reset": (I, [P]),

@@ -196,7 +196,8 @@ class SemiImplicitIterative:
     # ---- convergence control ----------------------------------------------
     def field_norm(self, what, level=1, kind=NORM_MAXABS):
         """read-only device reduction of a state field (pamg_field_norm): NORM_REF max(0, max), NORM_MAXABS
-        max |.|, NORM_L2 sqrt(sum of squares); the global value on a bound partition"""
+        max |.|, NORM_L2 sqrt(sum of squares), NORM_L1 sum |.|, NORM_L2_MASS the L2(Omega) norm of the P1 field
+        (sqrt of the sum of v^T M v over the sub-elements); the global value on a bound partition"""
         v = C.c_double()
         self._call("pamg_field_norm", level, what, kind, C.byref(v))
         return v.value
@@ -213,6 +214,18 @@ class SemiImplicitIterative:
         (pamg_residual_norm; solver 1 or 3, op = 1 on a handle created with monitor=1)"""
         v = C.c_double()
         self._call("pamg_residual_norm", level, kind, C.byref(v))
+        return v.value
+
+    def get_error(self):
+        """the reference's get_error (transport_tri_semi.F90:531-540): tracer(1)%error := |tnew - sin(x + y)| on
+        level 1, on the device (pamg_get_error); read it with get(ERROR) or field_norm(ERROR, 1, kind)"""
+        self._call("pamg_get_error")
+
+    def error_norm(self, kind=NORM_MAXABS):
+        """the same values reduced without being stored: the handle is untouched and the result equals
+        get_error() + field_norm(ERROR, 1, kind) on the float, for every kind (pamg_error_norm)"""
+        v = C.c_double()
+        self._call("pamg_error_norm", kind, C.byref(v))
         return v.value
 
     def solve(self, tol, max_cycles, check_every=1, kind=NORM_MAXABS):
