@@ -201,7 +201,24 @@ int pamg_tnn_level(pamg_handle *h);
 int pamg_write_vtu(pamg_handle *h, const char *path, int ascii);
 
 /* ---- the hot path, one entry per reference call site ---- */
-/* :316-317 told := tnew, tnew_nonlin := tnew, plus level-1 RHS (get_RHS :452-464) */
+/* :316-317 told := tnew, tnew_nonlin := tnew, plus level-1 RHS (get_RHS :452-464).
+ * Level 1's right-hand side. The reference assembles tracer(1)%RHS from told and the source inside every
+ * level-1 sweep and residual (get_RHS, :699-701, :865-867); within a time step told does not change, so every
+ * assembly gives the same array. The library assembles it once, here (solver 1 / 3; solver 2 assembles it in
+ * pamg_get_residual(1) only, as the reference's Richardson does, :865-867). The state after any sequence of
+ * calls is the reference's, with these documented differences, all of solver 1 / 3:
+ *  (a) between pamg_begin_timestep and the next level-1 smoother / residual call (a V-cycle included)
+ *      PAMG_RHS of level 1 already holds the new step's array where the reference still holds the previous
+ *      step's; before the first pamg_begin_timestep it is zero, so level 1 is smoothed only after one;
+ *  (b) a call that reads level 1's RHS without sweeping level 1 -- pamg_direct_solve(1),
+ *      pamg_field_norm(1, PAMG_RHS) -- reads the new step's array in that window;
+ *  (c) pamg_set_state(1, PAMG_TOLD) in mid-step moves the compact told copy of the halo at once but
+ *      not the RHS, and the next pamg_begin_timestep overwrites told (the reference's next sweep
+ *      assembles the RHS from it);
+ *  (d) pamg_set_state(1, PAMG_RHS) in mid-step stays in force until the next pamg_begin_timestep (the
+ *      reference overwrites it in its next sweep).
+ * tests/call_sequences.py drives random sequences of the public calls against the oracle and leaves out
+ * exactly these. */
 int pamg_begin_timestep(pamg_handle *h);
 /* :325-327, :346-348, :365-367 tnew_nonlin := tracer(l)%tnew */
 int pamg_copy_to_nonlin(pamg_handle *h, int level);
@@ -216,7 +233,8 @@ int pamg_restrictor(pamg_handle *h, int level);
 int pamg_get_residual(pamg_handle *h, int level);
 /* `call prolongator` splitting.F90:38-91 */
 int pamg_prolongator(pamg_handle *h, int level);
-/* n passes of the n_multigrid loop body :319-379 */
+/* n passes of the n_multigrid loop body :319-379; n = 0 is no pass: no field, halo word or flag changes,
+ * tnew_nonlin keeps the level it holds */
 int pamg_vcycle(pamg_handle *h, int n);
 /* the time loop :299-381 */
 int pamg_run(pamg_handle *h, int ntime, int n_multigrid);

@@ -1050,6 +1050,45 @@ void orc_free(orc_state *s) {
     free(s);
 }
 
+static void *dup_mem(const void *p, size_t bytes) {
+    if (!p) return NULL;
+    void *q = malloc(bytes ? bytes : 1);
+    memcpy(q, p, bytes);
+    return q;
+}
+
+/* A deep copy of the whole state (configuration, mesh, every field, tnew_nonlin, the halo arrays, the
+ * source override and the op = 1 tables): the model of a read-only call runs the writing routine on
+ * the copy (orc_get_residual, then a reduction of its residual) and throws it away. */
+orc_state *orc_clone(orc_state *s) {
+    orc_state *c = malloc(sizeof *c);
+    *c = *s;
+    const size_t U = (size_t)s->U;
+    c->X = dup_mem(s->X, sizeof(double) * 6 * U);
+    c->region = dup_mem(s->region, sizeof(int) * U);
+    c->neig = dup_mem(s->neig, sizeof(int) * 3 * U);
+    c->fneig = dup_mem(s->fneig, sizeof(int) * 3 * U);
+    c->dir = dup_mem(s->dir, sizeof(int) * 3 * U);
+    for (int l = 1; l <= s->c.levels; ++l) {
+        const size_t n = lvl_len(s, l) * sizeof(double), nsub = (size_t)s->nsub[l - 1];
+        c->tnew[l - 1] = dup_mem(s->tnew[l - 1], n);
+        c->told[l - 1] = dup_mem(s->told[l - 1], n);
+        c->rhs[l - 1] = dup_mem(s->rhs[l - 1], n);
+        c->res[l - 1] = dup_mem(s->res[l - 1], n);
+        c->source[l - 1] = dup_mem(s->source[l - 1], n);
+        c->detwei[l - 1] = dup_mem(s->detwei[l - 1], sizeof(double) * 3 * U);
+        c->nx[l - 1] = dup_mem(s->nx[l - 1], sizeof(double) * 18 * U);
+        c->fnb[l - 1] = dup_mem(s->fnb[l - 1], sizeof(int) * 3 * nsub);
+        c->fw[l - 1] = dup_mem(s->fw[l - 1], sizeof(double) * 9 * U);
+        c->fsx[l - 1] = dup_mem(s->fsx[l - 1], sizeof(int) * 3 * U);
+    }
+    c->tnn = dup_mem(s->tnn, lvl_len(s, s->tnn_level) * sizeof(double));
+    c->t_overlap = dup_mem(s->t_overlap, sizeof(double) * s->slots * 3 * U);
+    c->t_overlap_old = dup_mem(s->t_overlap_old, sizeof(double) * s->slots * 3 * U);
+    c->src_override = dup_mem(s->src_override, lvl_len(s, 1) * sizeof(double));
+    return c;
+}
+
 /* what: 0 tnew, 1 told, 2 rhs, 3 res, 4 tnn (level ignored), 5 source */
 static double *field(orc_state *s, int what, int l, size_t *n) {
     if (what == 4) { *n = lvl_len(s, s->tnn_level); return s->tnn; }

@@ -3094,6 +3094,9 @@ int pamg_prolongator(pamg_handle *h, int level) {
 
 int vcycle(pamg_handle *h, int n, bool dead_after) {
     CHK(check_level(h, 1));
+    // no pass of the loop body (:319): nothing is written -- not the step's constant halo words, which the
+    // fused forms put back before their first cycle, and not tnn_level, which every form sets after its last
+    if (n == 0) return PAMG_OK;
     // the fused op = 0 forms wait only for the exchange that read the send buffer they pack; the others may
     // touch anything an early exchange still in flight touches
     if (!(h->p.cycle == 0 && fused_ok(h))) CHK(settle(h));

@@ -47,6 +47,8 @@ def lib():
         L.orc_create.restype = P
         L.orc_create.argtypes = [C.POINTER(OrcCfg), C.c_int, dp, ip, ip, ip, ip]
         L.orc_free.argtypes = [P]
+        L.orc_clone.restype = P
+        L.orc_clone.argtypes = [P]
         L.orc_get.restype = C.c_long
         L.orc_get.argtypes = [P, C.c_int, C.c_int, C.c_void_p]
         L.orc_set.argtypes = [P, C.c_int, C.c_int, dp]
@@ -109,6 +111,18 @@ class Oracle:
         if getattr(self, "h", None):
             self.L.orc_free(self.h)
             self.h = None
+
+    def clone(self):
+        """a deep copy of the whole state (orc_clone): the model of a read-only call runs the writing routine
+        on it and throws it away"""
+        c = object.__new__(Oracle)
+        c.L, c.mesh, c.cfg, c.n_split, c.levels = self.L, self.mesh, self.cfg, self.n_split, self.levels
+        c.h = self.L.orc_clone(self.h)
+        assert c.h
+        return c
+
+    def tnn_level(self):
+        return self.L.orc_tnn_level(self.h)
 
     def nsub(self, level):
         return 4 ** (self.n_split - level + 1)
