@@ -223,7 +223,7 @@ __device__ __forceinline__ void st_halo(double *p, double x) {
 // the fused V-cycle writes TNEW only and leaves STATIC to k_overlap_static.
 // COH: the t_overlap words are written through (st_coh) for readers in other workgroups
 // SCOH: the tnew half of a send entry is written through (the resident call's early exchange reads
-// the send buffer while the launch still runs, pamg_api.cpp vcycle_fused)
+// the send buffer while the launch still runs, pamg_cycle.cpp vcycle_fused_resident)
 template <bool TNEW = true, bool STATIC = true, bool COH = false, bool SCOH = false>
 __device__ __forceinline__ void halo_face(const HaloArgs &H, int4 rec, int f, int i, const double t[3],
                                           const double to[3]) {

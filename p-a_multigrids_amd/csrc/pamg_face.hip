@@ -14,7 +14,7 @@
 // (oracle/pamg_oracle.c face_terms / face_sweep), so the results are bitwise its own. The forms:
 // per-colour kernels (k_face), one launch per sweep on LDS tiles (k_face_sweep), and a whole
 // smoother call in one cooperative launch for a level that fits on-chip (k_face_chain); the face
-// V-cycle (pamg_api.cpp vcycle_face_fused) strings them together. A grid-stride form that kept the
+// V-cycle (pamg_face_host.cpp vcycle_face_fused) strings them together. A grid-stride form that kept the
 // next tile in flight (two workgroups per CU) measured 5 % slower than one launch per tile and was
 // dropped (profiles/r03_c_face_ab.txt).
 #include <hip/hip_runtime.h>
@@ -1032,293 +1032,6 @@ __global__ __launch_bounds__(NT, RB ? (TS <= 256 ? (FOLD ? PAMG_FACE_PP_WAVES256
     tile(PAMG_FACE_PP_XCD ? xcd_tile(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x);
 }
 
-// ---- the wavefront call: every sweep of one smoother call on a level too large to stay on-chip
-// (levels 1 and 2 at n_split = 5: 8.4 M and 2.1 M sub-elements), each un_ele crossing HBM once per
-// call instead of once per sweep. A persistent cooperative grid of G workgroups takes un_eles in
-// ticket order (`order`: a reverse Cuthill-McKee numbering of the un_ele graph, host-built, band b);
-// a workgroup keeps its un_ele's iterate in LDS and its RHS in registers for the whole call and runs
-// sweep s once every neighbour has published its words for sweep s (flags[v] >= s, per un_ele), the
-// chain's hand-off (write-through halo words, drain, barrier, flag; ld_coh reads; snapshot buffers by
-// parity, safe for the chain's reason: a neighbour overwrites the buffer of sweep s - 1 only after
-// this un_ele has published sweep s, i.e. after it read that snapshot). Progress: the lowest
-// unfinished ticket t0 is resident, tickets [t0, t0 + G) are claimed, and a ticket in
-// [t0, t0 + G - k b) can always reach sweep k -- so G >= (run - 1) b + 1 (face_wave_ok) guarantees
-// the grid drains; the spins are bounded anyway (*tmo, as the chain). Every sub-element's arithmetic
-// is face_apply's on the same snapshot words, so the result is bitwise the per-sweep launches'.
-// Tagged halo granules (cdna_hip_programming.md 6 Guideline 16, R2: the data is the flag). A halo
-// double d of sweep s travels as two 8-byte words {lo32(d), tag}, {hi32(d), tag}, each one aligned
-// agent-scope atomic store (single-copy atomic), tag = the launch's tag base + s. A reader re-reads
-// both words (agent-scope atomic loads) until both carry the tag it expects, then has the exact
-// double: no flag, no drain, no fence, any number of workgroups per CU, and a tear between the two
-// words is caught by the tags. Granule buffers alternate by sweep parity as the snapshot buffers.
-typedef unsigned long long u64_t;
-__device__ __forceinline__ void st_gran(u64_t *g, double d, unsigned tag) {
-    const u64_t b = (u64_t)__double_as_longlong(d);
-    __hip_atomic_store((g_u64 *)g, (b & 0xffffffffull) | ((u64_t)tag << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store((g_u64 *)(g + 1), (b >> 32) | ((u64_t)tag << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// poll up to B granules at once (gi[b] < 0: none) into LDS (HI[li[b]]): every pending granule's two
-// words are requested together, so a round trip serves all of them; only the ones whose tags did not
-// match yet are re-read (bounded: *tmo set after 2^22 rounds)
-template <int B>
-__device__ __forceinline__ void gran_poll(const u64_t *gin, unsigned tag, const int64_t (&gi)[B], const int (&li)[B],
-                                          double *HI, unsigned *tmo) {
-    bool need[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) need[b] = gi[b] >= 0;
-    for (unsigned spins = 0;; ++spins) {
-        u64_t x[B], y[B];
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-            if (need[b]) {
-                x[b] = __hip_atomic_load((g_u64 *)const_cast<u64_t *>(gin + 2 * gi[b]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                y[b] = __hip_atomic_load((g_u64 *)const_cast<u64_t *>(gin + 2 * gi[b] + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        bool more = false;
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-            if (need[b]) {
-                if ((unsigned)(x[b] >> 32) == tag && (unsigned)(y[b] >> 32) == tag) {
-                    HI[li[b]] = __longlong_as_double((long long)((x[b] & 0xffffffffull) | (y[b] << 32)));
-                    need[b] = false;
-                } else {
-                    more = true;
-                }
-            }
-        if (!more) return;
-        if (spins > (1u << 22)) {
-            __hip_atomic_store((g_u32 *)tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
-// the next sweep's halo words of one sub-element as granules (update_overlaps, :555; halo_words'
-// destinations): a neighbour on this rank gets the granules of sweep `tag`, and, when fin, the plain
-// t_overlap word as well (the state the call leaves); the domain-boundary words (constant in a time
-// step) go plain into the snapshot buffer, at the call's first sweep (bc)
-__device__ __forceinline__ void halo_gran(const HaloArgs &H, const int4 rec[3], int h, const double t[3], bool bc,
-                                          u64_t *gout, unsigned tag, bool fin) {
-    const int pos[3] = {h & 1023, (h >> 10) & 1023, h >> 20};
-#pragma unroll
-    for (int f = 0; f < 3; ++f) {
-        const int i = pos[f];
-        if (!i) continue;
-        const int4 r = rec[f];
-        const int mode = r.x & 3;
-        if (mode == 0) {
-            if (!bc) continue;
-            const int a = (i - 1) * 3 + (f == 2 ? 1 : 0);
-            const int b = (i - 1) * 3 + (f == 1 ? 1 : 2);
-            const double2 v = H.bcv[r.z + i - 1];
-            H.tov[r.y + a] = v.x;
-            H.tov[r.y + b] = v.y;
-        } else if (mode == 1) {
-            const int k = (r.x >> 2) ? (H.m - i + 1) : i;
-            const int64_t d = r.y + (int64_t)(k - 1) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (gout) st_gran(gout + 2 * (d + c), t[c], tag);
-                if (fin) H.tov[d + c] = t[c];
-            }
-        }
-    }
-}
-
-constexpr int kWaveStampT = 32, kWaveStampW = 19;   // tickets per workgroup, stamps per ticket
-#ifndef PAMG_WAVE_WAVES
-#define PAMG_WAVE_WAVES 4
-#endif
-
-template <int TS, int NT, bool RB>
-__global__ __launch_bounds__(NT, TS <= 1024 ? PAMG_WAVE_WAVES : 1) void k_face_wave(
-    double *T, double *TNN, const double *SRC, const double *__restrict__ RHS, const double *__restrict__ stc,
-    const int4 *__restrict__ fnb, const double *__restrict__ fface, const int *__restrict__ fsx,
-    const int *__restrict__ cpos, int nup, double *buf0, double *buf1, u64_t *g0, u64_t *g1, unsigned tag0,
-    HaloArgs H, unsigned *flags, const int *__restrict__ order, unsigned *tmo, int U, int run, int total,
-    int store, int64_t pitch, int slots, int level1, double rdt, long long *stamps) {
-    using WS = WaveShape<TS, NT, RB>;
-    constexpr int PER = TS / NT, M = WS::M, NH = 9 * M, KU = WS::KU, KD = WS::KD;
-    static_assert(PER % 2 == 0 && M * M == TS, "whole un_ele tiles, adjacent pairs per thread");
-    __shared__ double X[3][TS];
-    __shared__ double HI[NH];
-    __shared__ double WD[24];
-    __shared__ int s_tk;
-    const int t = threadIdx.x;
-    unsigned *ticket = flags + U;   // the claim counter sits after the per-un_ele flags
-    int hp[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {   // face positions of the thread's halo pairs (the same in every un_ele)
-        const int4 e = H.hsub[2 * (t + NT * (q / 2)) + (q & 1)];
-        hp[q] = e.x | (e.y << 10) | (e.z << 20);
-    }
-    // the thread's items: the first colour (all positions for Jacobi), then the second
-    Items<KU> IA;
-    Items<KD> IB;
-#pragma unroll
-    for (int k = 0; k < KU; ++k) {
-        const int i = t + NT * k;
-        IA.j[k] = RB ? (i < nup ? cpos[i] : -1) : i;
-        IA.nb[k] = fnb[IA.j[k] < 0 ? 0 : IA.j[k]];
-    }
-#pragma unroll
-    for (int k = 0; k < KD; ++k) {
-        const int i = t + NT * k;
-        IB.j[k] = RB && i < TS - nup ? cpos[nup + i] : -1;
-        IB.nb[k] = fnb[IB.j[k] < 0 ? 0 : IB.j[k]];
-    }
-    // diagnostics (PAMG_WAVE_STAMPS): per ticket of workgroups 0..7 (the first kWaveStampT), wall
-    // clock at the claim, after the state's load, per sweep after the wait / snapshot / passes /
-    // publish, at the end
-    int nt_w = 0;
-    for (;;) {
-        if (t == 0) s_tk = (int)__hip_atomic_fetch_add((g_u32 *)ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const int tk = s_tk;
-        if (tk >= U) break;
-        long long *st = (stamps && t == 0 && blockIdx.x < 8 && nt_w < kWaveStampT)
-                            ? stamps + ((int64_t)blockIdx.x * kWaveStampT + nt_w) * kWaveStampW
-                            : nullptr;
-        ++nt_w;
-        if (st) st[0] = wall_clock64();
-        const int64_t u = __builtin_amdgcn_readfirstlane(order[tk]);
-        const int64_t s0 = u * TS;
-        int4 hf[3];
-#pragma unroll
-        for (int f = 0; f < 3; ++f) hf[f] = H.hface[3 * u + f];
-        FaceRec R;
-        load_face_rec(stc, fface, fsx, u, R);
-        if (t < 24) WD[t] = fface[u * kFaceStride + kFaceWD + t];
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int j = t + NT * k;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) X[c][j] = SRC[c * pitch + s0 + j];
-        }
-#pragma unroll
-        for (int k = 0; k < KU; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) IA.b[k][c] = IA.j[k] < 0 ? 0.0 : RHS[c * pitch + s0 + IA.j[k]];
-#pragma unroll
-        for (int k = 0; k < KD; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) IB.b[k][c] = IB.j[k] < 0 ? 0.0 : RHS[c * pitch + s0 + IB.j[k]];
-        // which of the un_ele's faces have a neighbour on this rank (their words arrive as granules;
-        // a domain-boundary face's words are constant and come with the sweep-0 snapshot)
-        const int nbm = ((hf[0].x & 3) == 1) | (((hf[1].x & 3) == 1) << 1) | (((hf[2].x & 3) == 1) << 2);
-        if (st) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            st[1] = wall_clock64();
-        }
-        auto xin = [&](int c, int q) { return X[c][q]; };
-        auto hv = [&](int64_t, int mf, int sp, int kk) { return HI[((mf - 1) * M + sp - 1) * 3 + kk]; };
-        auto rec = [&](int, int4 nb, auto &&f) { f(R, u, WD + 3 * face_pattern(nb), 0); };
-        for (int sw = 0; sw < run; ++sw) {
-            const double *tin = ((total - 1 - sw) & 1) ? buf1 : buf0;
-            double *tout = sw + 1 < total ? (((total - 2 - sw) & 1) ? buf1 : buf0) : nullptr;
-            // the items' positions and neighbour entries re-read in every sweep (small tables, cache
-            // hits) behind an opaque index, so that they and the LDS addresses derived from them are
-            // not held in registers across the sweep loop (VGPRs: occupancy)
-#pragma unroll
-            for (int k = 0; k < KU; ++k) {
-                int i = t + NT * k;
-                asm volatile("" : "+v"(i));
-                IA.j[k] = RB ? (i < nup ? cpos[i] : -1) : i;
-                IA.nb[k] = fnb[IA.j[k] < 0 ? 0 : IA.j[k]];
-            }
-#pragma unroll
-            for (int k = 0; k < KD; ++k) {
-                int i = t + NT * k;
-                asm volatile("" : "+v"(i));
-                IB.j[k] = RB && i < TS - nup ? cpos[nup + i] : -1;
-                IB.nb[k] = fnb[IB.j[k] < 0 ? 0 : IB.j[k]];
-            }
-            const int sk = 2 + 4 * (sw < 4 ? sw : 3);
-            if (st) st[sk] = wall_clock64();
-            if (sw == 0) {   // the call's snapshot of sweep 0 (the preceding halo launch wrote it)
-                for (int i = t; i < NH; i += NT) HI[i] = tin[u * slots * 3 + (int64_t)(i / (3 * M)) * slots + i % (3 * M)];
-            } else {         // the neighbours' granules of sweep sw, polled until every tag matches
-                constexpr int QB = (NH + NT - 1) / NT;   // the thread's snapshot words, polled together
-                int64_t gi[QB];
-                int li[QB];
-#pragma unroll
-                for (int q = 0; q < QB; ++q) {
-                    const int i = t + NT * q, f = i / (3 * M);
-                    li[q] = i;
-                    gi[q] = i < NH && ((nbm >> f) & 1) ? u * slots * 3 + (int64_t)f * slots + i % (3 * M) : -1;
-                }
-                gran_poll<QB>((sw & 1) ? g1 : g0, tag0 + (unsigned)sw, gi, li, HI, tmo);
-            }
-            // the call's last sweep: tnew := tnew_nonlin (:550), before the barrier that lets the passes
-            // rewrite X (a position's item may belong to another thread)
-            if (store == 1 && sw + 1 == run) {
-                int tt = t;   // opaque: the store addresses are not held across the sweep loop
-                asm volatile("" : "+v"(tt));
-#pragma unroll
-                for (int k = 0; k < PER; ++k)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) T[c * pitch + s0 + tt + NT * k] = X[c][tt + NT * k];
-            }
-            __syncthreads();
-            if (st) st[sk + 1] = wall_clock64();
-            if constexpr (RB) {   // up sub-elements, then down ones, in place (a colour reads only the other)
-                items_pass<0>(IA, xin, hv, rec, level1, rdt, [&](int k, const double r[3]) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) X[c][IA.j[k]] = r[c];
-                });
-                __syncthreads();
-                items_pass<1>(IB, xin, hv, rec, level1, rdt, [&](int k, const double r[3]) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) X[c][IB.j[k]] = r[c];
-                });
-            } else {   // Jacobi: every read of the old iterate before any write
-                double rj[KU][3];
-                items_pass<2>(IA, xin, hv, rec, level1, rdt, [&](int k, const double r[3]) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) rj[k][c] = r[c];
-                });
-                __syncthreads();
-#pragma unroll
-                for (int k = 0; k < KU; ++k)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) X[c][IA.j[k]] = rj[k][c];
-            }
-            __syncthreads();
-            if (st) st[sk + 2] = wall_clock64();
-            if (tout) {   // the next sweep's halo words (:550, :555 of sweep sw + 1) as granules
-                HaloArgs Hn = H;
-                Hn.tov = tout;
-                u64_t *gout = ((sw + 1) & 1) ? g1 : g0;
-                const unsigned tag = tag0 + (unsigned)(sw + 1);
-                const bool fin = sw + 2 == total;   // the words t_overlap keeps after the call
-                // granules only for a sweep this call runs (a dead last sweep has no reader)
-                if (sw + 1 >= run) gout = nullptr;
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    // opaque per sweep: the destinations are recomputed here instead of hoisted
-                    // out of the sweep loop (that held ~80 more VGPRs)
-                    int hq = hp[q];
-                    asm volatile("" : "+v"(hq));
-                    if (!hq) continue;
-                    const int j = 2 * (t + NT * (q / 2)) + (q & 1);
-                    const double tv[3] = {X[0][j], X[1][j], X[2][j]};
-                    halo_gran(Hn, hf, hq, tv, sw == 0, gout, tag, fin);
-                }
-            }
-            if (st) st[sk + 3] = wall_clock64();
-        }
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {   // tnew_nonlin (store 2: tnew, the dead last sweep's :550)
-            const int j = t + NT * k;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) (store == 2 ? T : TNN)[c * pitch + s0 + j] = X[c][j];
-        }
-        if (st) st[kWaveStampW - 1] = wall_clock64();
-        __syncthreads();   // s_tk and X are rewritten by the next ticket
-    }
-}
-
 // The co-residency guard of a chain launch. A chain's workgroups wait on each other's
 // flags, so they must all be resident at once; the launch checks the occupancy bound (launch_coresident),
 // but a CU-masked stream, another stream's kernels or another process can still hold CUs. Before touching any
@@ -1326,7 +1039,7 @@ __global__ __launch_bounds__(NT, TS <= 1024 ? PAMG_WAVE_WAVES : 1) void k_face_w
 // waited kGuardTicks (200 us) in vain it sets the abort bit in the same word -- by compare-and-swap, only while
 // the count is short, so either every workgroup proceeds or none does -- and counts the abort in *aborted.
 // Late arrivals see the bit and leave. An aborted launch leaves the state untouched: the host reads *aborted
-// and runs the call with one launch per sweep instead (pamg_api.cpp face_call). g[1] counts the workgroups
+// and runs the call with one launch per sweep instead (pamg_face_host.cpp face_call). g[1] counts the workgroups
 // leaving; the last one re-zeroes g[0] and g[1] for the next launch (stream order: nothing else runs on them).
 constexpr unsigned kGuardAbort = 0x80000000u;
 constexpr long long kGuardTicks = 20000;   // wall clock, 100 MHz
@@ -1364,7 +1077,7 @@ __device__ __forceinline__ bool chain_enter(unsigned *g, unsigned *aborted) {
 // The launch's gate (ChainGate, pamg_internal.h; null gate: the host reads *aborted after the launch): the last
 // workgroup out reports the launch in the host's pinned status ring (seq << 1 | aborted) and, when it ran, adds 1 to
 // the gate signal the stream waits on before the call's next launch -- an aborted launch leaves the stream waiting
-// until the host has run the fallback (pamg_api.cpp face_gates_drain)
+// until the host has run the fallback (pamg_face_host.cpp face_gates_drain)
 __device__ __forceinline__ void chain_leave(unsigned *g, const ChainGate &G) {
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1454,7 +1167,7 @@ __global__ __launch_bounds__(kChainNT, 1) void k_face_chain(double *T, double *T
     const int nhalo = ke * 9 * m;
     if constexpr (LREC) chain_load_recs(RS, stc, fface, fsx, u0, (int)std::min<int64_t>(ke, (N >> nsub_log2) - u0), t, NT);
     // with LREC the passes run over item lists (red-black: each colour over its positions, all lanes
-    // busy; Jacobi: the positions in order), as k_face_wave's
+    // busy; Jacobi: the positions in order)
     constexpr int KU = PER, KD = RB ? 1 : 0;
     Items<KU> IA;
     Items<KD == 0 ? 1 : KD> IB;
@@ -2273,7 +1986,7 @@ hipError_t launch_face_sweep_fused(hipStream_t s, const Level &L, const double *
     return hipGetLastError();
 }
 
-// Launch of a grid whose workgroups wait on each other (k_face_chain, k_face_wave): it must be resident
+// Launch of a grid whose workgroups wait on each other (k_face_chain): it must be resident
 // at once. hipLaunchCooperativeKernel checks that, but a process that used it crashed at exit under
 // rocprofv3's kernel trace -- SIGSEGV inside libhsa-runtime64, called from libamdhip64's exit-time
 // teardown, on a GPU mapping already gone (profiles/r04_a_face_exit.txt; the same probe without the
@@ -2473,82 +2186,6 @@ hipError_t launch_face_chain(hipStream_t s, const Level &L, int U, int cus, doub
             const long long hdr[4] = {pw ? -run : run, grid, E, L.nsub};
             fwrite(hdr, sizeof hdr, 1, fp);
             fwrite(h.data(), sizeof(long long), pw ? nst_pw : (size_t)8 * run * 4, fp);
-            fclose(fp);
-        }
-    }
-    return e;
-}
-
-// the wavefront call (k_face_wave): levels whose un_eles are 256, 1,024 or 4,096 sub-elements
-bool face_wave_shape(const Level &L) {
-    const int m = L.nsub == 256 ? 16 : L.nsub == 1024 ? 32 : L.nsub == 4096 ? 64 : 0;
-    // the colour lists' sizes are the kernel's compile-time item counts
-    return m && L.N % L.nsub == 0 && L.cpos && L.nup == m * (m + 1) / 2;
-}
-
-namespace {
-const void *face_wave_fn(int nsub, bool rb, int *nt) {
-    switch (nsub) {
-        case 4096: *nt = 1024; return rb ? (const void *)k_face_wave<4096, 1024, true> : (const void *)k_face_wave<4096, 1024, false>;
-        case 1024: *nt = 256; return rb ? (const void *)k_face_wave<1024, 256, true> : (const void *)k_face_wave<1024, 256, false>;
-        case 256: *nt = 64; return rb ? (const void *)k_face_wave<256, 64, true> : (const void *)k_face_wave<256, 64, false>;
-        default: *nt = 0; return nullptr;
-    }
-}
-}  // namespace
-
-// co-resident workgroups of the wavefront kernel for this level (0: not launchable)
-int face_wave_grid(const Level &L, bool rb, int cus) {
-    int nt = 0, per = 0;
-    const void *f = face_wave_fn(L.nsub, rb, &nt);
-    if (!f || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, f, nt, 0) != hipSuccess) return 0;
-    return per * cus;
-}
-
-hipError_t launch_face_wave(hipStream_t s, const Level &L, int U, int grid, double *tov, double *tov_b, double *tovo,
-                            unsigned long long *g0, unsigned long long *g1, unsigned tag0, unsigned *flags,
-                            const int *order, unsigned *tmo, int run, int total, int store, bool rb, bool level1,
-                            double rdt, int slots, bool from_T) {
-    if (L.N == 0 || run <= 0) return hipSuccess;
-    int nt = 0;
-    const void *f = face_wave_fn(L.nsub, rb, &nt);
-    if (!f || !face_wave_shape(L) || !L.fnb || grid <= 0) return hipErrorInvalidValue;
-    const HaloPlan &P = L.halo;
-    HaloArgs H{P.d_hsub, P.d_hface, P.d_bcv, P.d_told_halo, tov, tovo, P.d_send, 1 << L.isplit};
-    int l1 = level1 ? 1 : 0;
-    double *T = L.T, *TNN = L.TNN;
-    const double *RHS = L.RHS, *stc = L.stc, *fface = L.fface;
-    const int4 *fnb = L.fnb;
-    const int *fsx = L.fsx;
-    int64_t pitch = L.pitch;
-    hipError_t e = hipMemsetAsync(flags, 0, sizeof(unsigned) * ((size_t)U + 1), s);
-    if (e != hipSuccess) return e;
-    // PAMG_WAVE_STAMPS=<file>: append every launch's per-ticket phase stamps of workgroups 0..7
-    static const char *stamp_path = PAMG_STAMPS ? getenv("PAMG_WAVE_STAMPS") : nullptr;   // (diagnostics build)
-    long long *stamps = nullptr;
-    const size_t nst = (size_t)8 * kWaveStampT * kWaveStampW;
-    if (stamp_path) {
-        e = hipMalloc(&stamps, nst * sizeof(long long));
-        if (e != hipSuccess) return e;
-        e = hipMemsetAsync(stamps, 0, nst * sizeof(long long), s);
-        if (e != hipSuccess) return e;
-    }
-    const int g = std::min(grid, U);
-    const int *cpos = L.cpos;
-    int nup = L.nup;
-    const double *SRC = from_T ? L.T : L.TNN;
-    void *args[] = {&T, &TNN, &SRC, &RHS, &stc, &fnb, &fface, &fsx, &cpos, &nup, &tov, &tov_b, &g0, &g1, &tag0, &H, &flags,
-                    &order, &tmo, &U, &run, &total, &store, &pitch, &slots, &l1, &rdt, &stamps};
-    e = launch_coresident(f, g, nt, args, s);
-    if (stamp_path) {
-        std::vector<long long> hs(nst);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipMemcpy(hs.data(), stamps, nst * sizeof(long long), hipMemcpyDeviceToHost);
-        (void)hipFree(stamps);
-        if (FILE *fp = fopen(stamp_path, "ab")) {
-            const long long hdr[4] = {run, g, U, L.nsub};
-            fwrite(hdr, sizeof hdr, 1, fp);
-            fwrite(hs.data(), sizeof(long long), nst, fp);
             fclose(fp);
         }
     }

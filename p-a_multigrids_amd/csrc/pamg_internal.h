@@ -96,7 +96,7 @@ struct Level {
     double *SRC = nullptr;
     // level 1 only: tracer(1)%error = |tnew - sin(x + y)| (get_error, transport_tri_semi.F90:531-540), three planes
     // of its own, allocated zero-filled on the first pamg_get_error / pamg_get_state / pamg_field_norm of
-    // PAMG_ERROR (pamg_api.cpp error_setup): a run that never asks for it keeps its footprint
+    // PAMG_ERROR (pamg_norm_host.cpp error_setup): a run that never asks for it keeps its footprint
     double *ERR = nullptr;
     double *stc = nullptr;            // U_local * kStcStride
     int2 *subinfo = nullptr;          // nsub: (irow, ipos) of get_str_info, by storage position
@@ -164,7 +164,7 @@ struct Timing {
     double bytes[PAMG_K_COUNT] = {0};
 };
 
-struct Comm;  // pamg_api.cpp
+struct Comm;  // pamg_host.h
 
 // the record one reduction pass over a level produces (pamg_norm.hip): the identities are
 // max = -inf, maxabs = 0, sumsq = 0; nonfinite != 0: some input was NaN or +-inf (fmax drops a NaN)
@@ -231,10 +231,11 @@ struct pamg_handle {
     pamg::Comm *comm = nullptr;
     double *scratch = nullptr; size_t scratch_bytes = 0;
     // op = 1: the local un_eles' neighbours (0-based local ids, -1: none or another rank), 3 per un_ele
+    // (the chain's workgroup neighbour lists, face_chain_setup)
     std::vector<int> neig_local;
-    unsigned *chain_tmo = nullptr;   // give-up word of the face chain's / wavefront's bounded spins
+    unsigned *chain_tmo = nullptr;   // give-up word of the face chain's bounded spins
                                      // ([1..2] the chain's co-residency guard, [3] its aborts)
-    bool chain_pending = false;      // a chain or wavefront launch ran since face_chain_check last read it
+    bool chain_pending = false;      // a chain launch ran since face_chain_check last read it
     // the guarded chain launches' gates (face_call, PAMG_CHAIN_GATE): the stream waits on `gate` (signal
     // memory) after each launch for the count the launch adds when it ran; an aborted one leaves the stream
     // waiting until the host has run the call's fallback (face_gates_drain) -- the host no longer waits for
@@ -249,14 +250,6 @@ struct pamg_handle {
     };
     std::vector<GatePending> gates;   // in stream order, not yet read back
     hipStream_t stream_fb = nullptr;  // the gated fallback's launches (the handle's stream waits at the gate)
-    // the face operator's wavefront calls (k_face_wave; lazy, single domain): the ticket order (a
-    // reverse Cuthill-McKee numbering of neig_local), its band, the neighbours on the device and the
-    // per-un_ele flags + ticket counter
-    int *wave_order = nullptr, *wave_neig = nullptr;
-    unsigned *wave_flags = nullptr;
-    int wave_band = -1;
-    unsigned long long *wave_gran = nullptr;   // two granule buffers, 2 words per t_overlap double each
-    unsigned wave_tag = 1;                     // tag base of the next wavefront launch
     // the resident call's per-cycle exchange (halo_exchange = 1): per-cycle workgroup counters and
     // the signal the comm stream waits on (cycles published so far: xc_sig_base after the last call)
     unsigned *xc_done = nullptr;
@@ -274,7 +267,7 @@ struct pamg_handle {
     hipEvent_t xe_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool xe_ev_valid = false;
     int cus = 0;                     // compute units of the device
-    // op = 1 on a partition: the coarsest level agglomerated (pamg_api.cpp agg_*). `agg` is a
+    // op = 1 on a partition: the coarsest level agglomerated (pamg_face_host.cpp agg_*). `agg` is a
     // replica handle holding only level L of the WHOLE mesh, un_eles renumbered so that every rank's are one
     // block (agg_off[r] .. agg_off[r + 1]); it shares this handle's stream. Each cycle gathers the ranks' level-L
     // RHS into it and every rank runs the single-domain coarsest calls (the persistent chain) on its own copy.
@@ -372,7 +365,7 @@ hipError_t launch_vcycle_fine(hipStream_t s, const Level *lv, int L, int U, int 
 // stores as keep says; rhsf: the launch starts the time step (as launch_vcycle_fine's)
 // steps > 1 (rhsf): a whole pamg_run -- `steps` time steps of `cycles` cycles, each step starting
 // with told := tnew and its RHS -- in one launch (vcycle_resident_run_supported)
-// the early per-call exchange (pamg_api.cpp vcycle_fused): the workgroups take the tiles in tile_map's
+// the early per-call exchange (pamg_cycle.cpp vcycle_fused_resident): the workgroups take the tiles in tile_map's
 // order (remote tiles first); each tile with a face on another rank counts its end in *done once its send
 // words are written through, and the one whose count reaches `target` (the running total of remote-tile
 // ends, mod 2**32: the counter is never reset) adds 1 to *sig
@@ -460,17 +453,6 @@ hipError_t launch_face_pp(hipStream_t s, const Level &L, int K, const double *in
 // workgroups inside the launch; store 1: tnew (the last sweep's start) and tnew_nonlin, 2: tnew :=
 // the result (dead last sweep)
 bool face_chain_fits(int nsub, int U, int cus);
-// the wavefront form of one smoother call (k_face_wave, levels of 256 / 1,024 / 4,096 sub-elements
-// per un_ele): un_eles claimed in the ticket order `order`, flags = U per-un_ele words + the ticket
-// counter (zeroed here); g0 / g1 the tagged halo granules of odd / even sweeps (2 words per t_overlap
-// double), tag0 + s the tag of sweep s (never reused: the host advances it past every launch's tags);
-// grid = co-resident workgroups
-bool face_wave_shape(const Level &L);
-int face_wave_grid(const Level &L, bool rb, int cus);
-hipError_t launch_face_wave(hipStream_t s, const Level &L, int U, int grid, double *tov, double *tov_b, double *tovo,
-                            unsigned long long *g0, unsigned long long *g1, unsigned tag0, unsigned *flags,
-                            const int *order, unsigned *tmo, int run, int total, int store, bool rb, bool level1,
-                            double rdt, int slots, bool from_T = false);
 int face_chain_per_wg(int nsub, int U, int cus);
 // a chain launch's gate report (pamg_face.hip chain_leave; gate null: none)
 constexpr unsigned long long kGateRing = 1024;

@@ -90,13 +90,13 @@ struct VArgs {
     // the resident launch with an exchange after every cycle (part 6, halo_exchange = 1): cycle c <
     // cycles - 1 packs the tnew words of its remote halo entries into ring + c ring_stride (3 per
     // entry); each workgroup counts the cycle in xc_done[c] and the one that completes it adds 1 to
-    // *xc_sig, the signal the comm stream waits on (pamg_api.cpp vcycle_fused)
+    // *xc_sig, the signal the comm stream waits on (pamg_cycle.cpp vcycle_fused_resident)
     double *ring;
     int64_t ring_stride;
     unsigned *xc_done;
     unsigned long long *xc_sig;
     unsigned xc_grid;
-    // the resident call with its per-call exchange started early (pamg_api.cpp vcycle_fused): tile_map
+    // the resident call with its per-call exchange started early (pamg_cycle.cpp vcycle_fused_resident): tile_map
     // (non-null) gives workgroup b the tile tile_map[b] -- the tiles holding a face whose neighbour is on
     // another rank first, so that they finish in the first round; each such tile counts its end in
     // *xe_done after its last cycle's send words are drained (written through), and the one whose count
@@ -1684,7 +1684,7 @@ __global__ __launch_bounds__(512, L >= 5 ? PAMG_RES_WAVES : PAMG_RESB_WAVES) voi
 }
 
 // ===================================================================== resident corrected call
-// The corrected V-cycle (pamg_params.cycle = 1; pamg_api.cpp vcycle_corrected,
+// The corrected V-cycle (pamg_params.cycle = 1; pamg_cycle.cpp vcycle_corrected,
 // oracle orc_vcycle_corrected): the reference's levels, smoother (transport_tri_semi.F90:491-507),
 // residual (:725-873, with the b - A x sign), restrictor (splitting.F90:10-32, 146-151) and the P1
 // interpolation its prolongator cascade encodes (splitting.F90:59-88), with the defects of the

@@ -2,7 +2,7 @@
 untitled8192 at N = 1, 2, 4, 8 ranks, simulated on one GPU (rank 0's partition, detached: the halo
 refresh and the sweeps of every rank run, the exchange itself does not -- its latency is the RCCL
 transport's, a multi-GPU node's), beside the single domain's fused cycle. On a partition every sweep of
-levels 1-2 is the halo refresh, the exchange and one tile launch (pamg_api.cpp smooth, op = 1): no
+levels 1-2 is the halo refresh, the exchange and one tile launch (pamg_cycle.cpp smooth, op = 1): no
 two-sweep passes, which need the neighbours' iterate inside the launch. Level 3 is agglomerated (round 6):
 each cycle gathers the ranks' level-3 RHS into a replica of the whole level and every rank runs the
 single-domain chain on it; a detached rank copies only its own block, so the gather's cross-GPU part is

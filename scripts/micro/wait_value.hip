@@ -1,6 +1,6 @@
 // Probe: can a stream wait (hipStreamWaitValue64) on a counter that a running kernel on another
-// stream raises with a system-scope atomic? (the resident call's per-cycle exchange, pamg_api.cpp
-// vcycle_fused, halo_exchange = 1). Signal memory (hipMallocSignalMemory) and, for comparison,
+// stream raises with a system-scope atomic? (the resident call's per-cycle exchange, pamg_cycle.cpp
+// vcycle_fused_resident, halo_exchange = 1). Signal memory (hipMallocSignalMemory) and, for comparison,
 // plain device memory. Every wait is bounded on the host (hipStreamQuery polling, 5 s).
 #include <hip/hip_runtime.h>
 

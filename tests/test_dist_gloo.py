@@ -5,7 +5,7 @@ reference halo.
 
 Each rank owns an x-strip of untitled8192.msh. The rank's level fields are the
 oracle's (pinned to the reference); packing, the per-peer exchange (ordered
-like the grouped ncclSend/ncclRecv of pamg_api.cpp `halo`) and unpacking run
+like the grouped ncclSend/ncclRecv of pamg_comm.cpp `exchange`) and unpacking run
 here with numpy + torch.distributed(gloo), and every rank's t_overlap /
 t_overlap_old must equal the oracle's single-domain buffers on its elements.
 """

@@ -219,12 +219,12 @@ def test_face_fused_cycle_equals_per_step_sequence(mesh, S, L, solver, ns):
 @pytest.mark.parametrize("mesh,S,L,solver,ns,n", [
     ("untitled8192.msh", 5, 3, 3, 4, 2), ("untitled8192.msh", 5, 2, 1, 3, 1), ("untitled8192.msh", 4, 3, 3, 4, 2),
     ("900_ele.msh", 5, 3, 3, 4, 2), ("irregular.msh", 6, 2, 3, 3, 1)])
-def test_face_wavefront_call_equals_per_sweep_launches(mesh, S, L, solver, ns, n, monkeypatch):
-    """The wavefront form of a smoother call (k_face_wave: un_eles claimed in reverse Cuthill-McKee
-    ticket order, each sweep started once the neighbours have published their words, the iterate in
-    LDS across the call) leaves the state of one launch per sweep, bit for bit -- on levels of 256,
-    1,024 and 4,096 sub-elements per un_ele, with far more un_eles than co-resident workgroups
-    (untitled8192 at S = 5: 8,192 level-1 un_eles over 512 workgroups), red-black and Jacobi."""
+def test_face_chain_call_equals_per_sweep_launches(mesh, S, L, solver, ns, n, monkeypatch):
+    """The persistent chain of a smoother call (k_face_chain: the coarsest level's call in one launch, the
+    iterate in LDS across it, the halo words handed from workgroup to workgroup between sweeps), the
+    default, leaves the state of one launch per sweep (PAMG_FACE_CHAIN=0), bit for bit -- the fused face
+    cycle's one-sweep calls on levels of 256, 1,024 and 4,096 sub-elements per un_ele around it
+    (untitled8192 at S = 5: 8,192 level-1 un_eles), red-black and Jacobi, over two time steps."""
     import pamg
     m = pamg.Mesh.read(os.path.join(goldens.MESHES, mesh))
 
@@ -238,11 +238,9 @@ def test_face_wavefront_call_equals_per_sweep_launches(mesh, S, L, solver, ns, n
         g.close()
         return st, ov
 
-    monkeypatch.setenv("PAMG_FACE_PP", "0")   # the fused cycle's one-sweep calls, where the wavefront form applies
-    monkeypatch.setenv("PAMG_FACE_WAVE", "0")
+    monkeypatch.setenv("PAMG_FACE_PP", "0")   # the fused cycle's one-sweep calls
     monkeypatch.setenv("PAMG_FACE_CHAIN", "0")
     rs, rov = run()
-    monkeypatch.setenv("PAMG_FACE_WAVE", "1")
     monkeypatch.setenv("PAMG_FACE_CHAIN", "1")
     gs, gov = run()
     assert_identical(gs, rs)

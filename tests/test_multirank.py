@@ -191,7 +191,7 @@ def test_local_group_early_per_call_exchange(mesh, S, L, nparts, kind, how):
     """halo_exchange = 0 on a partition: the resident call's per-call exchange starts early -- the tiles
     holding a remote face run first (the launch's tile order), count their ends once their send words are
     written through, and the last raises the device signal on which the comm stream starts the exchange
-    while the other tiles run (pamg_api.cpp vcycle_fused). One early exchange per
+    while the other tiles run (pamg_cycle.cpp vcycle_fused_resident). One early exchange per
     vcycle call; the state is the single domain's bit for bit."""
     m = pamg.Mesh.read(os.path.join(goldens.MESHES, mesh))
     full = pamg.SemiImplicitIterative(m, S, L, fused=0, arith=1)
