@@ -22,6 +22,12 @@ Level 1's source term is the reference's in-place cascade (get_RHS, transport_tr
 M_12 f_2 and s'_2 = M_20 s'_0 + M_21 s'_1 + M_22 f_2. It is NOT M f (12 % off at dt = 0.05);
 `source_level1` restates the cascade, and every method that needs s' also takes it as an input.
 
+The block-diagonal operator of op = 0 is here too (A0 = M/dt + k K1, D0 = ml/dt + k diag K1, its sweep
+and its exact solve per sub-element). One level at a time is all this module knows: what joins the
+levels -- the restrictor, the P1 interpolation -- and the corrected V-cycle composed from these sweeps
+are in tests/cycle_model.py, found from coordinates in the same way and held against the oracle and the
+HIP path in tests/test_cycle_model.py.
+
 Fields go in and come out in the reference's shape (3, nsub, U); results are np.longdouble.
 """
 import copy
@@ -221,6 +227,43 @@ class FaceModel:
             step = wD * (b - self.apply(x1, x_inner=x1, x_outer=x0))
             x1[:, colour, :] += step[:, colour, :]
         return x1
+
+    # ---- the volume operator alone (op = 0): block-diagonal, one 3 x 3 block per sub-element
+    @property
+    def A0(self):
+        """the blocks M/dt + k K1, (U, nsub, 3, 3)"""
+        return self.M / self.dt + self.k * self.K1
+
+    @property
+    def D0(self):
+        """the diagonal of op = 0's smoother, ml/dt + k diag(K1), (3, nsub, U)"""
+        return self._out(self.ml / self.dt + self.k * np.einsum("usii->usi", self.K1))
+
+    def apply0(self, x):
+        """A0 x"""
+        return self._out(np.einsum("usij,usj->usi", self.A0, self._in(x)))
+
+    def sweep0(self, x, rhs):
+        """one sweep x + omega/D0 (rhs - A0 x) of op = 0: Jacobi within a sub-element, and nothing couples two
+        sub-elements, so solver 1 and solver 3 are the same sweep"""
+        x0 = np.asarray(x, LD)
+        return x0 + self.omega / self.D0 * (np.asarray(rhs, LD) - self.apply0(x0))
+
+    def solve0(self, rhs):
+        """A0^-1 rhs per sub-element by Cramer's rule in long double (numpy's solve has no long double)"""
+        A, b = self.A0, self._in(rhs)
+
+        def det(m):
+            return (m[..., 0, 0] * (m[..., 1, 1] * m[..., 2, 2] - m[..., 1, 2] * m[..., 2, 1])
+                    - m[..., 0, 1] * (m[..., 1, 0] * m[..., 2, 2] - m[..., 1, 2] * m[..., 2, 0])
+                    + m[..., 0, 2] * (m[..., 1, 0] * m[..., 2, 1] - m[..., 1, 1] * m[..., 2, 0]))
+
+        d, cols = det(A), []
+        for i in range(3):
+            Ai = A.copy()
+            Ai[..., :, i] = b
+            cols.append(det(Ai) / d)
+        return self._out(np.stack(cols, axis=-1))
 
 
 def rel_diff(got, model):

@@ -7,6 +7,12 @@ prolongator encodes, and fixes those defects (oracle/pamg_oracle.c
 orc_vcycle_corrected). No reference output exists for it: the HIP path is pinned to
 the oracle restatement, whose every building block (smoother, residual products,
 restrictor, geometry) is pinned to the reference (tests/test_oracle_golden.py).
+What the restatement cannot show about itself -- the child / node tables of the
+transfers as the corrected cycle uses them, the cycle's composition (the b - A x
+sign, coarse levels from zero, where the correction is added, n_coarse calls) and the
+direct coarse solve inside it -- is pinned independently in tests/test_cycle_model.py:
+the oracle and the HIP path against a model built from vertex coordinates
+(tests/cycle_model.py).
 Tolerance (check_corrected): every field's error is measured against the level-1 field of
 its kind (tnew-like against max|tnew_L1|, RHS / residual against max|RHS_L1|, the halo
 against its own max), at 1e-12. Level 1 is then held to 1e-12 relative; the coarse levels
